@@ -11,6 +11,12 @@ SDP_Solver::step) over the synthetic "3d Ising mixed-correlator" SDP C4 of SURVE
 metric is quoted on; it fits one GPU, so it is the workload at every N (strong scaling:
 blocks shard across ranks, Q' is summed with one integer all-reduce).  Inputs are resident
 in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W warm-up and K timed steps from the initial point and prints the line.
+--full adds what takes runs of its own: the parity gate on the committed oracle fixture before the
+timed steps, one profiled iteration after them (per-stage milliseconds), the device copy bandwidth
+of the roofline and the CPU baseline.  --dump-outputs DIR writes the state the last timed step
+left (what a caller of SDPSolver.iterate() reads back) as float64 .npy files, see dump_outputs().
 """
 from __future__ import annotations
 
@@ -255,6 +261,74 @@ def syrk_source_digest() -> str:
     return hashlib.sha1(txt[a:b].encode()).hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def _records_to_f64(rec):
+    """float64 values of mpf_t-layout records (count, 2 + limbs64) as SDPSolver.array_mpf returns them (mw_host.hpp:
+    to_mpf_record): word 0 the signed limb count, word 1 the exponent in 64-bit limbs, then the limbs, least significant
+    first; value = sign * sum_i d[i] 2^(64 (exp - |size| + i)).  The two most significant limbs decide a float64."""
+    import numpy as np
+    size = rec[:, 0].view(np.int64)
+    used = np.abs(size)
+    exp = np.clip(rec[:, 1].view(np.int64), -40, 40)   # |value| outside 2^(+-2560) is inf / 0 in float64 anyway
+    rows = np.arange(len(rec))
+    out = np.zeros(len(rec))
+    for k in (1, 2):
+        limb = rec[rows, 2 + np.maximum(used - k, 0)].astype(np.float64)
+        out += np.where(used >= k, np.ldexp(limb, 64 * (exp - k)), 0.0)
+    return np.where(size < 0, -out, out)
+
+
+def dump_outputs(solver, directory, rank=0, world=1):
+    """--dump-outputs: what the last timed step left behind, as a caller of SDPSolver.iterate() reads it back, in float64:
+    scalars.npy (the iteration's scalars in the order of sdpb_amd.solver.ITERATION_KEYS), y.npy (N), x.npy (the blocks' x
+    one after the other) and X.npy / Y.npy (every block's even then odd parity matrix, column-major, one after the other).
+    Above DUMP_LIMIT_BYTES in all, a fixed sample of blocks (a permutation seeded with 0, taken while it fits, then in
+    block order) stands for the whole.  The block arrays live on their owning rank: every rank reads its own and rank 0
+    gathers and writes them (with --simulate-world only the blocks of rank 0 exist)."""
+    import numpy as np
+    from sdpb_amd.solver import ITERATION_KEYS
+    sdp = solver.sdp
+    scalars = np.array([float(solver.scalar(k)) for k in ITERATION_KEYS])
+    y = _records_to_f64(solver.array_mpf("y", limbs64=2))
+    sizes = []
+    for m, K in zip(sdp.dims, sdp.num_points):
+        even = m * ((K + 1) // 2)
+        sizes.append(K * m * (m + 1) // 2 + 2 * (even * even + (m * K - even) ** 2))
+    budget = (DUMP_LIMIT_BYTES - 8 * (scalars.size + y.size)) // 8
+    if sum(sizes) <= budget:
+        chosen = list(range(sdp.J))
+    else:
+        chosen, used = [], 0
+        for j in np.random.default_rng(0).permutation(sdp.J):
+            if used + sizes[j] <= budget:
+                chosen.append(int(j))
+                used += sizes[j]
+        chosen.sort()
+    mine = {}
+    for j in chosen:
+        if solver.block_owner(j) != rank:
+            continue
+        mine[j] = {"x": _records_to_f64(solver.array_mpf("x", j, limbs64=2))}
+        for name in ("X", "Y"):
+            mine[j][name] = np.concatenate([_records_to_f64(solver.array_mpf(name, j, parity, limbs64=2)) for parity in (0, 1)])
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(mine, parts, dst=0)
+        if rank != 0:
+            return
+        for p in parts:
+            mine.update(p)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "scalars.npy"), scalars)
+    np.save(os.path.join(directory, "y.npy"), y)
+    blocks = [mine[j] for j in chosen if j in mine]
+    for name in ("x", "X", "Y"):
+        np.save(os.path.join(directory, f"{name}.npy"), np.concatenate([b[name] for b in blocks]) if blocks else np.zeros(0))
+
+
 def _self_launch(args) -> int:
     """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one
     rank per GPU (the driver may also launch the ranks itself; then WORLD_SIZE is set and this
@@ -290,6 +364,8 @@ def dry_run(args, lib, rank, world):
         solver.set_collectives(*make_collectives(torch.device("cpu")))
     for _ in range(args.warmup + args.steps):
         assert not solver.iterate(), solver.terminate_reason
+    if args.dump_outputs:
+        dump_outputs(solver, args.dump_outputs, rank, world)
     obj = solver.scalar("P-obj")
     if world > 1:
         objs = [None] * world
@@ -434,9 +510,14 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("SDPB_BENCH_WORKLOAD", "C4"),
                     help="C3 | C4 (default: the config the metric is quoted on) | C5slice | golden:<case> (e.g. golden:singlet_cT)")
     ap.add_argument("--scale", type=float, default=float(os.environ.get("SDPB_BENCH_SCALE", "1.0")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate before the timed steps, one profiled iteration after them, the device copy "
+                         "bandwidth of the roofline and the CPU baseline (a plain run does the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left as float64 .npy files under DIR (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-full", action="store_true",
-                    help="CPU baseline at FULL size (one steady-state iteration of the port, minutes) instead of the bounded sample")
+                    help="with --full: CPU baseline at FULL size (one steady-state iteration of the port, minutes) instead of the bounded sample")
     ap.add_argument("--exchange", default=os.environ.get("SDPB_BENCH_EXCHANGE", "auto"), choices=["auto", "rccl", "callbacks"],
                     help="world > 1: auto = the in-library RCCL communicator if its pre-flight passes, else torch.distributed "
                          "(backend nccl = RCCL) behind the C-ABI callbacks; rccl / callbacks force one")
@@ -580,21 +661,19 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    # parity gate BEFORE anything is timed; then back to the initial point, so the timed
-    # iterations are W+1 .. W+K of the run, as in every earlier round
+    # --full: parity gate BEFORE anything is timed; then back to the initial point, so the timed
+    # iterations are W+1 .. W+K of the run with or without it
     dog.enter("parity gate", solver)
-    if sim:
-        gate = None
-    elif golden:
-        gate = golden_gate(solver, golden, golden_fixture)
-    else:
-        gate = parity_gate(solver, args.workload, args.scale, precision)
+    gate = None
+    if args.full and not sim:
+        gate = golden_gate(solver, golden, golden_fixture) if golden else parity_gate(solver, args.workload, args.scale, precision)
     if gate and gate["passed"] is False:
         if rank == 0:
             emit({"metric": f"interior-point iterations/sec at --precision {precision}", "value": None,
                   "PARITY_GATE_FAILED": True, "parity_gate": gate})
         raise SystemExit("bench.py: the device iteration does not reproduce the oracle fixture; no value reported")
-    solver.reset()
+    if gate:
+        solver.reset()
 
     # The synthetic SDP is not feasible: SDP_Solver::run ends it with "maxComplementarity exceeded" after 49
     # iterations (profiles/c4_iterations_to_termination.py).  A run longer than that starts over from the initial
@@ -640,17 +719,24 @@ def main():
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    # per-stage breakdown: one extra, UNTIMED iteration with the stage timers on (they synchronise
+    if args.dump_outputs:
+        dog.enter("dump outputs")
+        dump_outputs(solver, args.dump_outputs, rank, world)
+    # --full: per-stage breakdown: one extra, UNTIMED iteration with the stage timers on (they synchronise
     # the stream at every stage boundary, so they are off inside the timed region)
-    dog.enter("profiled iteration")
-    solver.set_profiling(True)
-    if solver.iteration >= 40 or (golden and solver.iteration >= len(golden["iterations"]) - 2):   # keep clear of the termination
-        solver.reset()
-        solver.iterate()
-    tp0 = solver.timers()
-    assert not solver.iterate(), solver.terminate_reason
-    tp1 = solver.timers()
-    solver.set_profiling(False)
+    stages = None
+    if args.full:
+        dog.enter("profiled iteration")
+        solver.set_profiling(True)
+        if solver.iteration >= 40 or (golden and solver.iteration >= len(golden["iterations"]) - 2):   # keep clear of the termination
+            solver.reset()
+            solver.iterate()
+        tp0 = solver.timers()
+        assert not solver.iterate(), solver.terminate_reason
+        tp1 = solver.timers()
+        solver.set_profiling(False)
+        skip = ("kernel.", "host_syncs", "iterations", "comm.", "launches")
+        stages = {k: round(tp1[k] - tp0.get(k, 0.0), 3) for k in tp1 if not k.startswith(skip)}
     dog.disarm()
 
     try:
@@ -690,16 +776,16 @@ def main():
             else:
                 traffic_source = ("dropped: profiles/pmc_k_syrk_fx.json was measured on kernel source digest "
                                   f"{rec.get('kernel_source_digest')}, this build is {syrk_source_digest()}")
-        skip = ("kernel.", "host_syncs", "iterations", "comm.", "launches")
-        stages = {k: round(tp1[k] - tp0.get(k, 0.0), 3) for k in tp1 if not k.startswith(skip)}
         nl = solver.limbs
-        from sdpb_amd.solver import copy_bandwidth_gbs
-        copy_gbs = copy_bandwidth_gbs(1 << 30, 5, lib_path=args.lib)
+        copy_gbs = None
+        if args.full:
+            from sdpb_amd.solver import copy_bandwidth_gbs
+            copy_gbs = copy_bandwidth_gbs(1 << 30, 5, lib_path=args.lib)
         hashes = [r.get("sequence_hash") for r in per_rank]
         out = {
             "metric": f"interior-point iterations/sec at --precision {precision}",
             "value": value, "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "full": args.full,
             "dtype": f"mw{32 * nl} (fixed-width multi-word float, {nl}x32-bit limbs; Q syrk: exact integer product of a fixed-point image with {solver.fx_frac_bits} fraction bits)",
             "data": "reference end-to-end test SDP" if golden else "synthetic",
             "config": {"workload": label,
@@ -763,7 +849,7 @@ def main():
                                           "6 MPI ranks on the reference authors' CPU", "same_input": True}
         if sim:
             out["SIMULATED_WORLD_NOT_A_MEASUREMENT"] = sim
-        if world == 1 and not args.no_cpu_baseline and not golden:
+        if args.full and world == 1 and not args.no_cpu_baseline and not golden:
             out["cpu_baseline"] = cpu_baseline(args.workload, precision, full=args.cpu_full)
         emit(out)
     solver.close()

@@ -8,7 +8,7 @@ for v in sdpb_amd/_variants/*.so; do
   n=$(basename $v .so)
   cp $v sdpb_amd/libsdpb_hip.so
   for rep in 1 2; do
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_C4_$n.json 2>> $O/err.log
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_C4_$n.json 2>> $O/err.log
   python - "$O/bench_C4_$n.json" <<'PY'
 import json,sys
 try:

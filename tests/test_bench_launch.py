@@ -45,6 +45,32 @@ def test_bench_under_the_drivers_launcher_and_single_rank_agree():
         assert b != 0 and abs(a - b) <= mpmath.mpf(2) ** -200 * abs(b)   # rank-order sums differ in the last bits only
 
 
+def test_bench_dump_outputs_are_the_state_of_the_last_step_and_reproducible(tmp_path):
+    """--dump-outputs DIR: float64 .npy files of what the last step left (scalars, y, x, X, Y), identical from run to run;
+    with 2 ranks rank 0 gathers the other rank's blocks, so the files have the same shapes and agree up to the
+    rank-order sums."""
+    import numpy as np
+    names = ["X.npy", "Y.npy", "scalars.npy", "x.npy", "y.npy"]
+    args = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--workload", "C2", "--dump-outputs"]
+    one = _run(args + [str(tmp_path / "a")], {})
+    _run(args + [str(tmp_path / "b")], {})
+    _run(args[:2] + ["--gpus", "2"] + args[2:] + [str(tmp_path / "c")], {})
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(os.listdir(tmp_path / "c")) == names
+    total = 0
+    for n in names:
+        a, b, c = (np.load(tmp_path / d / n) for d in "abc")
+        assert a.dtype == np.float64 and a.size and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        assert c.shape == a.shape and np.allclose(c, a, rtol=2.0 ** -40, atol=0), n
+        total += a.nbytes
+    assert total <= 64e6
+    from sdpb_amd.solver import ITERATION_KEYS
+    p_obj = np.load(tmp_path / "a" / "scalars.npy")[ITERATION_KEYS.index("P-obj")]
+    assert p_obj == float(one["P-obj"])
+    # y has N entries
+    assert np.load(tmp_path / "a" / "y.npy").size == int(one["config"]["workload"].split("N=")[1])
+
+
 class _Replay:
     """A stand-in for SDPSolver that replays a fixture (optionally with one field of one iteration perturbed): the gate's
     own logic is what is under test here, no device, no library."""
