@@ -2253,11 +2253,31 @@ template <int FX> constexpr int fx_frac_bits()
 {
   return fx_toom5k<FX>() ? 5 * toom_wb<FX>() - 1 : fx_toom4<FX>() ? 4 * toom_wb<FX>() - 1 : fx_two_level<FX>() ? 32 * FX - 7 : 32 * FX - 3;
 }
+// TILE COLUMN ORDER of the lazy-carry image (fx_toom5k): inside every group of 32 columns -- a tile of k_syrk_fx3 -- column c
+// sits in slot 2 (c % 16) + (c % 32) / 16, so that the two pieces a lane of that kernel multiplies (columns l and l + 16 of
+// the tile) are 16 contiguous bytes of the staged row: one ds_read_b128 per operand and row.  Every other image keeps its
+// columns in their natural order (the identity).
+template <int FX> constexpr int fx_col_slot(int c) { return fx_toom5k<FX>() ? 32 * (c / 32) + 2 * (c % 16) + (c % 32) / 16 : c; }
+// slots per image row: with the tile column order the last group of a row has holes between its real columns (fewer than
+// 32 of them still reach up to slot 31), so the row is padded to whole groups of 32 slots
+template <int FX> constexpr size_t fx_row_slots(size_t cols) { return fx_toom5k<FX>() ? (cols + 31) / 32 * 32 : cols; }
+// image element of entry idx = r N + c of a row-major rows x N operand (or of a window of its rows)
+template <int FX> MW_HD size_t fx_elem(size_t idx, int N)
+{
+  if constexpr(fx_toom5k<FX>())
+    return idx / (size_t)N * fx_row_slots<FX>((size_t)N) + (size_t)fx_col_slot<FX>((int)(idx % (size_t)N));
+  else
+    return idx;
+}
 // elements per group plane of the image of a rows x cols operand: k_syrk_fx3 stages whole blocks of `rb` rows and
-// whole 32-column tiles without bounds checks, so its image is padded (the pad is zeroed once, when the image is allocated)
+// whole 32-column tiles without bounds checks, so its image is padded (the pad is zeroed once, when the image is allocated):
+// rows to a multiple of rb, and behind the last row 64 elements for the columns past N of the last tile -- which, in the
+// natural column order, load whatever follows the row.  The lazy-carry image (tile column order) pads EVERY row to a
+// multiple of 32 slots instead (fx_row_slots): a staged tile never leaves its row, no real column's slot falls outside it,
+// and the holes of the last group are part of the zero pad (k_normalize_fx / k_fx_from_int never write them).
 template <int FX> constexpr size_t fx_image_stride(size_t rows, size_t cols, int rb)
 {
-  return fx_toom4k<FX>() ? (rows + rb - 1) / rb * rb * cols + 64 : rows * cols;
+  return fx_toom4k<FX>() ? (rows + rb - 1) / rb * rb * fx_row_slots<FX>(cols) + 64 : rows * cols;
 }
 // edge of the output tiles of the syrk kernel in use: k_syrk_fx3 gives a lane 2 x 2 outputs
 template <int FX> constexpr int syrk_tile_edge() { return fx_toom4k<FX>() ? 32 : 16; }
@@ -2888,7 +2908,7 @@ template <int Z> MW_HD void toom4_interpolate(uint32_t (&w)[7][Z])
   z_sub<Z>(w[5], w[1]);                 // W5 -= W1
 }
 
-// fx[idx] = image of trunc(PT[idx] * inv_norm[idx % N] * 2^FB)
+// fx[fx_elem(idx)] = image of trunc(PT[idx] * inv_norm[idx % N] * 2^FB)
 template <int NL, int FX>
 __global__ void __launch_bounds__(WG) k_normalize_fx(mw::CPtr PT, size_t count, int N, mw::CPtr inv_norm, uint32_t *fx, size_t fx_stride)
 {
@@ -2929,14 +2949,15 @@ __global__ void __launch_bounds__(WG) k_normalize_fx(mw::CPtr PT, size_t count, 
 #pragma unroll
       for(int i = 0; i < FX; ++i)
         v[i] = sat ? ((i == FX - 1) ? ((1u << (FB % 32)) - 1u) : 0xffffffffu) : w[i]; // 2^FB - 1 for either image (FB = 32FX-3 or 32FX-7)
-      fx_store<FX>(v, t.neg != 0, fx, fx_stride, idx);
+      fx_store<FX>(v, t.neg != 0, fx, fx_stride, fx_elem<FX>(idx, N));
     }
 }
 
 // the same image from staged planes: plane 0 = sign, planes 1..FX = |v| (sdpb_hip_op_int_syrk);
 // in and out are distinct buffers
-// (in_stride = elements per staged plane; `in` may point at a row window of the staged matrix)
-template <int FX> __global__ void __launch_bounds__(WG) k_fx_from_int(const uint32_t *in, size_t in_stride, size_t count, uint32_t *fx, size_t fx_stride)
+// (in_stride = elements per staged plane; `in` may point at a row window of the staged matrix, rows of N entries)
+template <int FX>
+__global__ void __launch_bounds__(WG) k_fx_from_int(const uint32_t *in, size_t in_stride, size_t count, int N, uint32_t *fx, size_t fx_stride)
 {
   const size_t idx = (size_t)blockIdx.x * WG + threadIdx.x;
   if(idx >= count)
@@ -2945,7 +2966,7 @@ template <int FX> __global__ void __launch_bounds__(WG) k_fx_from_int(const uint
 #pragma unroll
   for(int i = 0; i < FX; ++i)
     v[i] = in[(size_t)(i + 1) * in_stride + idx];
-  fx_store<FX>(v, in[idx] != 0, fx, fx_stride, idx);
+  fx_store<FX>(v, in[idx] != 0, fx, fx_stride, fx_elem<FX>(idx, N));
 }
 
 // Column sums S_n = sum_r a'_rn, as (2FX+2)-limb integers stored behind the N x N
@@ -3983,13 +4004,20 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK_WAVES)
 // reads as the 4 x 4-limb product of k_syrk_fx2, and the same staging: 16-byte global_load_lds units of a row of
 // adjacent columns' pieces, [row][column][M3 limbs] in LDS.  Quadrants of the tile that hold no output (above the
 // diagonal of a diagonal tile, past column N) are skipped workgroup-wide, so the executed products are those of the
-// 16 x 16 tiling.  One SWEEP over the split's rows = one of the 21 products: a pass per block of RBG rows, the column
+// 16 x 16 tiling.  In lazy-carry mode (fx_toom5k) the image is in TILE COLUMN ORDER (fx_col_slot: columns l and l + 16 of a
+// tile in slots 2 l and 2 l + 1, image rows padded to whole groups of 32 slots), so the staged row -- still a verbatim copy
+// of 256 bytes of the image row -- holds a lane's two pieces of an operand as 16 contiguous bytes: ONE ds_read_b128 per
+// operand and row (4 LDS-array cycles, conflict-free, at full rate from one wavefront per SIMD) where the natural order
+// needs a ds_read2_b64 (8 cycles); the products and the output planes are the same.  One SWEEP over the split's rows = one of the 21 products: a pass per block of RBG rows, the column
 // accumulators (96 bits each, 4 x (2 M3 - 1) per lane) live in registers for the whole sweep and are folded when it ends.
 #ifndef SDPB_SYRK3_PREFETCH
 #define SDPB_SYRK3_PREFETCH 1 // measured on C4 (profiles/r04s_syrk3_variants.txt): 101.9 ms against 103.8 without
 #endif
 #ifndef SDPB_SYRK3_WAVES
 #define SDPB_SYRK3_WAVES 3
+#endif
+#ifndef SDPB_SYRK3_LAZY_TRIP
+#define SDPB_SYRK3_LAZY_TRIP 32 // rows per trip of the lazy-carry row loop: the whole pass, every row's LDS offset an immediate
 #endif
 #ifndef SDPB_SYRK3_NBUF
 #define SDPB_SYRK3_NBUF 2 // staging buffers of the lazy-carry mode; 3 (requests two passes ahead) was measured: no gain, see below
@@ -4063,7 +4091,9 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   // Staging of the NEXT pass: the image is padded with zero rows to a multiple of RBG and every row block a workgroup
   // touches lies inside it (fx3_image_stride), so a pass is the same per-lane offsets from a workgroup-uniform base:
   // no per-lane pointer selects.  Columns past N load whatever follows the row (the pad behind the last one): they
-  // only reach outputs that are not stored.
+  // only reach outputs that are not stored.  (LAZY: an image row is NS = fx_row_slots(N) slots, whole tiles, and the slots
+  // of the columns past N are zero pad.)
+  const size_t NS = fx_row_slots<FX>((size_t)N);
   uint32_t va[DIRECT ? 1 : GL][4], vb[DIRECT ? 1 : GL][4];
   uint32_t offa[GL], offb[GL];
 #pragma unroll
@@ -4071,11 +4101,11 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     {
       const int e = threadIdx.x + t * WG;
       const int unit = e % UPR, rr = e / UPR;
-      offa[t] = (uint32_t)(((size_t)rr * N + ti * 32) * M3 + 4 * unit);
-      offb[t] = (uint32_t)(((size_t)rr * N + tj * 32) * M3 + 4 * unit);
+      offa[t] = (uint32_t)(((size_t)rr * NS + ti * 32) * M3 + 4 * unit);
+      offb[t] = (uint32_t)(((size_t)rr * NS + tj * 32) * M3 + 4 * unit);
     }
   auto fetch = [&](int g, unsigned r0, int into) __attribute__((always_inline)) {
-    const uint32_t *base = fx + ((size_t)g * fx_stride + (size_t)r0 * (size_t)N) * M3;
+    const uint32_t *base = fx + ((size_t)g * fx_stride + (size_t)r0 * NS) * M3;
 #pragma unroll
     for(int t = 0; t < GL; ++t)
       {
@@ -4129,8 +4159,13 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     // pass (vmcnt(0)) before the first read of this one -- those land in the other buffer; the barrier that ends the
     // pass waits for them
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sa + buf * NPAIR * 4 + li * M3);
-    const uint32_t lb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sb + buf * NPAIR * 4 + lj * M3);
+    // LAZY (tile column order, fx_col_slot): the pieces of columns l and l + 16 of the tile are the 16 bytes at 16 l of the
+    // staged row -- one ds_read_b128 per operand and row, .x/.y the piece of column l, .z/.w that of column l + 16.  The 16
+    // lanes of a read's lane group that differ in li cover 256 contiguous bytes (every bank once); those that differ in lj
+    // read at most two 16-byte units (a broadcast each).  Else: the two pieces are 16 columns = 128 bytes apart (ds_read2_b64).
+    constexpr int LSTEP = LAZY ? 2 * M3 : M3;
+    const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sa + buf * NPAIR * 4 + li * LSTEP);
+    const uint32_t lb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sb + buf * NPAIR * 4 + lj * LSTEP);
 #define FX3_P(C, H, X, Y) "v_mad_u64_u32 %" #C ", vcc, %" #X ", %" #Y ", %" #C "\n\tv_addc_co_u32 %" #H ", vcc, 0, %" #H ", vcc\n\t"
 #define FX3_L(C, X, Y) "v_mad_u64_u32 %" #C ", vcc, %" #X ", %" #Y ", %" #C "\n\t"
 #define FX3_MAC_BOTH(o0, o1, a0x, a0y, a1x, a1y, bx, by)                                                                                   \
@@ -4184,10 +4219,18 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     else                                                                                                                                   \
       FX3_MAC_ONE(0, va.x, va.y, vb.x, vb.y);                                                                                              \
   }
+    // LAZY: one 128-bit read per operand, the row's byte offset in the instruction's immediate
+#define FX3L_ROW(ROW)                                                                                                                      \
+  {                                                                                                                                        \
+    u32x4 va, vb;                                                                                                                          \
+    asm volatile("ds_read_b128 %0, %2 offset:%4\n\tds_read_b128 %1, %3 offset:%4\n\ts_waitcnt lgkmcnt(0)"                                  \
+                 : "=&v"(va), "=&v"(vb)                                                                                                    \
+                 : "v"(xa), "v"(xb), "n"((ROW) * 256)                                                                                      \
+                 : "memory");                                                                                                              \
+    FX3_MACS(va, vb)                                                                                                                       \
+  }
     static_assert(RBG % 4 == 0 && M3 == 2, "four rows per trip, offsets in units of 8 bytes");
-#if SDPB_SYRK3_PREFETCH
-    // The reads of row r + 1 are issued before the products of row r: two register sets, each handed from the
-    // statement that issues its reads to the statement that waits for them without the compiler touching it in between.
+    // the products of one row for the quadrants of MASK
 #define FX3_MACS(va, vb)                                                                                                                   \
   if constexpr(MASK == 15)                                                                                                                 \
     {                                                                                                                                      \
@@ -4206,6 +4249,9 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     }                                                                                                                                      \
   else                                                                                                                                     \
     FX3_MAC_ONE(0, va.x, va.y, vb.x, vb.y);
+#if SDPB_SYRK3_PREFETCH
+    // The reads of row r + 1 are issued before the products of row r: two register sets, each handed from the
+    // statement that issues its reads to the statement that waits for them without the compiler touching it in between.
     // wait for the set (wa, wb) that is in flight, then issue the reads of (ra, rb)
 #ifdef SDPB_SYRK3_EXPERIMENT_HALF_LDS
     // TIMING EXPERIMENT ONLY (wrong results): the pieces of the second operand are not read -- what the kernel would cost
@@ -4223,40 +4269,102 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
                : "v"(xa), "v"(xb)                                                                                                          \
                : "memory")
 #endif
+    // LAZY: wait for the set (wa, wb), then issue the two 128-bit reads of row ROW of the trip into (ra, rb); the row's
+    // byte offset (256 ROW, at most 32 rows: 8192) is the instruction's immediate, so a trip needs no address arithmetic
+#define FX3L_NEXT(wa, wb, ra, rb, ROW)                                                                                                     \
+  asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %2, %4 offset:%6\n\tds_read_b128 %3, %5 offset:%6"                                   \
+               : "+v"(wa), "+v"(wb), "=&v"(ra), "=&v"(rb)                                                                                  \
+               : "v"(xa), "v"(xb), "n"((ROW) * 256)                                                                                        \
+               : "memory")
+#define FX3L_ROWS2(R)                                                                                                                      \
+  FX3L_NEXT(a0, b0, a1, b1, (R) + 1);                                                                                                      \
+  FX3_MACS(a0, b0)                                                                                                                         \
+  FX3L_NEXT(a1, b1, a0, b0, (R) + 2);                                                                                                      \
+  FX3_MACS(a1, b1)
+#define FX3L_ROWS8(R) FX3L_ROWS2(R) FX3L_ROWS2((R) + 2) FX3L_ROWS2((R) + 4) FX3L_ROWS2((R) + 6)
     u32x4 a0, b0, a1, b1;
-    {
-      const uint32_t xa = la, xb = lb;
-      asm volatile("ds_read2_b64 %0, %2 offset0:0 offset1:16\n\tds_read2_b64 %1, %3 offset0:0 offset1:16" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
-    }
-#pragma unroll 1
-    for(int rr = 0; rr < RBG; rr += 4)
+    if constexpr(LAZY)
       {
-        const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
-        FX3_NEXT(a0, b0, a1, b1, 32, 48);
-        FX3_MACS(a0, b0)
-        FX3_NEXT(a1, b1, a0, b0, 64, 80);
-        FX3_MACS(a1, b1)
-        FX3_NEXT(a0, b0, a1, b1, 96, 112);
-        FX3_MACS(a0, b0)
-        // row rr + 4; past the last row of the pass this reads the first row of the other buffer (or, behind sb, LDS
-        // that is not ours): the data is dropped
-        FX3_NEXT(a1, b1, a0, b0, 128, 144);
-        FX3_MACS(a1, b1)
+        // TRIP rows per trip of the loop (SDPB_SYRK3_LAZY_TRIP: 8, 16 or 32; a whole pass where it divides RBG)
+        constexpr int TRIP = (RBG % SDPB_SYRK3_LAZY_TRIP == 0) ? SDPB_SYRK3_LAZY_TRIP : 8;
+        static_assert(RBG % 8 == 0 && (TRIP == 8 || TRIP == 16 || TRIP == 32) && RBG * 256 < 65536, "whole trips, the offsets fit 16 bits");
+        {
+          const uint32_t xa = la, xb = lb;
+          asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
+        }
+#pragma unroll 1
+        for(int rr = 0; rr < RBG; rr += TRIP)
+          {
+            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words (folded away when a trip is the pass)
+            // the last read of the last trip is row RBG: the first row of the other buffer (or, behind the last buffer,
+            // the 64 words sa / sb carry for it: 16 li + 16 <= 256 bytes); the data is dropped
+            FX3L_ROWS8(0)
+            if constexpr(TRIP >= 16)
+              {
+                FX3L_ROWS8(8)
+              }
+            if constexpr(TRIP >= 32)
+              {
+                FX3L_ROWS8(16)
+                FX3L_ROWS8(24)
+              }
+          }
+      }
+    else
+      {
+        {
+          const uint32_t xa = la, xb = lb;
+          asm volatile("ds_read2_b64 %0, %2 offset0:0 offset1:16\n\tds_read2_b64 %1, %3 offset0:0 offset1:16" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
+        }
+#pragma unroll 1
+        for(int rr = 0; rr < RBG; rr += 4)
+          {
+            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
+            FX3_NEXT(a0, b0, a1, b1, 32, 48);
+            FX3_MACS(a0, b0)
+            FX3_NEXT(a1, b1, a0, b0, 64, 80);
+            FX3_MACS(a1, b1)
+            FX3_NEXT(a0, b0, a1, b1, 96, 112);
+            FX3_MACS(a0, b0)
+            // row rr + 4; past the last row of the pass this reads the first row of the other buffer (or, behind sb, LDS
+            // that is not ours): the data is dropped
+            FX3_NEXT(a1, b1, a0, b0, 128, 144);
+            FX3_MACS(a1, b1)
+          }
       }
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(b0)::"memory");
+#undef FX3L_ROWS8
+#undef FX3L_ROWS2
+#undef FX3L_NEXT
 #undef FX3_NEXT
-#undef FX3_MACS
 #else
-#pragma unroll 1
-    for(int rr = 0; rr < RBG; rr += 4)
+    if constexpr(LAZY)
       {
-        const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
-        FX3_ROW(0, 16)
-        FX3_ROW(32, 48)
-        FX3_ROW(64, 80)
-        FX3_ROW(96, 112)
+#pragma unroll 1
+        for(int rr = 0; rr < RBG; rr += 4)
+          {
+            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
+            FX3L_ROW(0)
+            FX3L_ROW(1)
+            FX3L_ROW(2)
+            FX3L_ROW(3)
+          }
+      }
+    else
+      {
+#pragma unroll 1
+        for(int rr = 0; rr < RBG; rr += 4)
+          {
+            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
+            FX3_ROW(0, 16)
+            FX3_ROW(32, 48)
+            FX3_ROW(64, 80)
+            FX3_ROW(96, 112)
+          }
       }
 #endif
+#undef FX3_MACS
+#undef FX3L_ROW
 #undef FX3_ROW
 #undef FX3_MAC_ONE
 #undef FX3_MAC_BOTH
@@ -4266,8 +4374,10 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
       }
     else
       {
-        // column x of the tile sits at word M3 x of a staged row: the lane's two pieces are 16 columns apart
-        const uint32_t *pa = sa + buf * NPAIR * 4 + li * M3, *pb = sb + buf * NPAIR * 4 + lj * M3;
+        // column x of the tile sits at word M3 x of a staged row: the lane's two pieces are 16 columns apart -- or, in the
+        // tile column order of the lazy-carry image (fx_col_slot), neighbours: columns l and l + 16 in slots 2 l and 2 l + 1
+        constexpr int LSTEP = LAZY ? 2 * M3 : M3, SECOND = LAZY ? M3 : 16 * M3;
+        const uint32_t *pa = sa + buf * NPAIR * 4 + li * LSTEP, *pb = sb + buf * NPAIR * 4 + lj * LSTEP;
 #pragma unroll SDPB_SYRK2_UNROLL
         for(int rr = 0; rr < RBG; ++rr)
           {
@@ -4275,9 +4385,9 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
             piece_load<M3>(pa + rr * ROWW, a0);
             piece_load<M3>(pb + rr * ROWW, b0);
             if constexpr((MASK & 10) != 0)
-              piece_load<M3>(pa + rr * ROWW + 16 * M3, a1);
+              piece_load<M3>(pa + rr * ROWW + SECOND, a1);
             if constexpr((MASK & 12) != 0)
-              piece_load<M3>(pb + rr * ROWW + 16 * M3, b1);
+              piece_load<M3>(pb + rr * ROWW + SECOND, b1);
             if constexpr(LAZY)
               {
                 auto lazy = [&](const uint32_t (&x)[M3], const uint32_t (&y)[M3], uint64_t (&cs)[2 * M3 - 1]) {
@@ -4511,7 +4621,7 @@ __global__ void __launch_bounds__(WG) k_fx_colsum5(const uint32_t *fx, size_t fx
   if(col < N)
     for(unsigned r = r_begin + phase; r < r_end; r += 4)
       {
-        const size_t e = (size_t)r * N + col;
+        const size_t e = (size_t)r * fx_row_slots<FX>((size_t)N) + (size_t)fx_col_slot<FX>(col); // (the partial sums are indexed by the true column)
 #pragma unroll
         for(int u = 0; u < G; ++u)
           {

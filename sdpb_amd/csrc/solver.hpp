@@ -1968,7 +1968,7 @@ private:
     if(!one_chunk && image_words_for(rows, (size_t)N) > w.budget_words)
       {
         // the most rows whose image fits, in whole passes of the product kernel
-        const size_t per_row = (size_t)N * fx_planes<FX>();
+        const size_t per_row = fx_row_slots<FX>((size_t)N) * fx_planes<FX>();
         const size_t fixed = (size_t)64 * fx_planes<FX>() + 4;
         size_t fit = w.budget_words > fixed ? (w.budget_words - fixed) / per_row : 0;
         fit = fit / quantum * quantum;
@@ -3179,7 +3179,8 @@ public:
     syrk_G_windows(win, (unsigned)rows, cols, fx, acc.p, as, acc2, partial.p, (const uint32_t *)tl.p, part, tu.p,
                    [&](size_t r0, unsigned nr) {
                      const size_t n = (size_t)nr * cols;
-                     launch(k_fx_from_int<FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, (const uint32_t *)staged.p + r0 * (size_t)cols, cnt, n, fx.p, win.stride);
+                     launch(k_fx_from_int<FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, (const uint32_t *)staged.p + r0 * (size_t)cols, cnt, n, cols,
+                            fx.p, win.stride);
                    },
                    [] {});
     launch(k_syrk_unbias<FX>, dim3(cdiv((size_t)cols * cols, WG)), dim3(WG), stream_, acc.p, as, cols, (unsigned long long)rows, (size_t)0,

@@ -106,13 +106,15 @@ def q_window(rows: int, N: int, nl: int, image_budget_bytes: int):
     """solver.hpp: Solver::q_window -- (rows per input window, windows, bytes of the window's image)."""
     fx, words, edge, planes, rb, waves, toom4, toom4k = _fx(nl)
 
+    slots = -(-N // 32) * 32 if fx == 16 else N   # kernels.hpp: fx_row_slots (tile column order of the lazy-carry image)
+
     def image_bytes(r):
-        stride = (-(-r // rb) * rb * N + 64) if toom4k else r * N
+        stride = (-(-r // rb) * rb * slots + 64) if toom4k else r * N
         return (max(stride, 1) * words + 4) * 4
     r = max(rows, 1)
     budget_words = max(1, image_budget_bytes // 4)
     if image_bytes(r) // 4 > budget_words:
-        per_row = N * words
+        per_row = slots * words
         fixed = 64 * words + 4
         fit = ((budget_words - fixed) // per_row if budget_words > fixed else 0) // rb * rb
         fit = max(fit, rb)
