@@ -526,9 +526,6 @@ constexpr int TR = WG / PB;
 #define SDPB_TRSM_KC 4
 #endif
 constexpr int TRSM_KC = PB < SDPB_TRSM_KC ? PB : SDPB_TRSM_KC; // columns per LDS-staged operand chunk of the panel kernels
-#ifndef SDPB_TRSM_ALIAS
-#define SDPB_TRSM_ALIAS 1 // measured on C4 (profiles/r04t_trsm_variants.txt): P = L^-1 B 35.1 -> 34.1 ms, 34.8 -> 34.4 / 34.1 ms on another box
-#endif
 // ... of the two Cholesky panel kernels (k_chol_panel_solve, chol_syrk_tile): half the barriers per term
 #ifndef SDPB_CHOL_KC
 #define SDPB_CHOL_KC SDPB_TRSM_KC
@@ -826,14 +823,11 @@ MW_HD void trsm_rlt_tile(const Batch &L, const Batch &Li, const Batch &X, const 
   // itself for the in-place solve, or another array with X's descriptors -- P = L^{-1} B reads B and writes P, which
   // saves the 3-GB device-to-device copy per iteration the in-place form needed in front of it (round 5)
   constexpr int KC = TRSM_KC, ROWS = WG / COLS, SXN = ROWS * KC, SLN = COLS * KC, STN = ROWS * COLS;
-#if SDPB_TRSM_ALIAS
   // the T tile of the second phase lies over the X chunk of the first (whose last pass ends with a barrier): 384
-  // instead of 416 numbers of LDS per workgroup = five workgroups per CU instead of four
+  // instead of 416 numbers of LDS per workgroup = five workgroups per CU instead of four (P = L^-1 B 35.1 -> 34.1 ms on
+  // C4, profiles/r04t_trsm_variants.txt)
   static_assert(SXN <= STN, "the X chunk fits under the T tile");
   uint32_t *st = smem, *sx = smem, *sl = smem + (NL + 2) * STN;
-#else
-  uint32_t *sx = smem, *sl = sx + (NL + 2) * SXN, *st = sl + (NL + 2) * SLN;
-#endif
   if((int)(blockIdx.x * ROWS) >= dx.rows)
     return;
   const int rl = threadIdx.x % ROWS, j = threadIdx.x / ROWS;
@@ -899,13 +893,8 @@ template <int NL> __global__ void __launch_bounds__(WG) k_trsm_rlt_panel(Batch L
   if(k0 >= dl.rows)
     return;
   const int nb = dl.rows - k0 < PB ? dl.rows - k0 : PB;
-  // X chunk + L chunk + T tile: (WG/COLS + COLS) KC + WG numbers, largest at COLS = PB and COLS = 8
-  constexpr int MINC = PB < 8 ? PB : 8, NMAX = (WG / MINC + MINC) * KC > (WG / PB + PB) * KC ? (WG / MINC + MINC) * KC : (WG / PB + PB) * KC;
-#if SDPB_TRSM_ALIAS
+  // T tile (over the X chunk) + L chunk: WG + COLS KC numbers, largest at COLS = PB
   __shared__ uint32_t smem[(NL + 2) * (WG + PB * KC)];
-#else
-  __shared__ uint32_t smem[(NL + 2) * (NMAX + WG)];
-#endif
   if constexpr(PB >= 32)
     {
       if(nb <= 8)
@@ -1024,11 +1013,6 @@ __global__ void __launch_bounds__(WG) k_td_image_L(Batch L, Batch Li, const int 
 #ifndef SDPB_TD_KC
 #define SDPB_TD_KC 4 // k-slices of the right operand's image per LDS pass of the tile dot products
 #endif
-#ifndef SDPB_TD_PREFETCH
-#define SDPB_TD_PREFETCH 0 // 1: the next slice of the right operand requested before the products of this one.  Measured and
-                           // left off: Q.solve 29.6 against 27.5 ms on C4 (three more 16-byte registers per lane spill at
-                           // the 128 VGPRs that four workgroups per CU allow; profiles/r06r_variants.txt)
-#endif
 #ifndef SDPB_TD_TRSM_WG_PER_CU
 #define SDPB_TD_TRSM_WG_PER_CU 4 // measured on C4 (profiles/r06b_variants.txt): 2 / 3 / 4 workgroups per CU (208 / 168 / 128 VGPRs) 36.9 / 32.6 / 31.2 ms
 #endif
@@ -1040,40 +1024,9 @@ MW_HD void td_tile_product(td::Cols<W> &g, const uint32_t *sX, uint32_t *sL, con
   constexpr int SL_WORDS = KC * PB * W;
   static_assert(SL_WORDS % 4 == 0, "16-byte moves of a slice");
   td::cols_zero<W>(g);
-#if SDPB_TD_PREFETCH
-  // the slice of the NEXT pass is requested before the products of this one and written to LDS when they are done: the
-  // round trip to L2 (every workgroup of a block streams the same tile image) is no longer exposed at every barrier
-  constexpr int NQ = (SL_WORDS / 4 + WG - 1) / WG;
-  td::Quad pre[NQ];
-  auto request = [&](int c) {
-    const td::Quad *gsrc = reinterpret_cast<const td::Quad *>(tile_img + (size_t)c * PB * W);
-#pragma unroll
-    for(int u = 0; u < NQ; ++u)
-      {
-        const int f = threadIdx.x + u * WG;
-        if(f < SL_WORDS / 4)
-          pre[u] = gsrc[f];
-      }
-  };
-  request(0);
-#endif
   for(int c = 0; c < PB; c += KC)
     {
-#if SDPB_TD_PREFETCH
-      {
-        td::Quad *dst = reinterpret_cast<td::Quad *>(sL);
-#pragma unroll
-        for(int u = 0; u < NQ; ++u)
-          {
-            const int f = threadIdx.x + u * WG;
-            if(f < SL_WORDS / 4)
-              dst[f] = pre[u];
-          }
-      }
-      __syncthreads();
-      if(c + KC < PB) // (workgroup-uniform: `terms` differs between the wavefronts of a diagonal tile, the slice is everybody's)
-        request(c + KC);
-#else
+      // (requesting the next slice before the products of this one spills and is slower: profiles/r06r_variants.txt)
       {
         const td::Quad *gsrc = reinterpret_cast<const td::Quad *>(tile_img + (size_t)c * PB * W);
         td::Quad *dst = reinterpret_cast<td::Quad *>(sL);
@@ -1081,7 +1034,6 @@ MW_HD void td_tile_product(td::Cols<W> &g, const uint32_t *sX, uint32_t *sL, con
           dst[f] = gsrc[f];
       }
       __syncthreads();
-#endif
       if(ok)
         {
 #pragma unroll 1
@@ -1234,14 +1186,11 @@ MW_HD void trsm_rln_tile(const Batch &L, const Batch &Li, const Batch &X, const 
                          uint32_t *smem)
 {
   constexpr int KC = TRSM_KC, ROWS = WG / COLS, SXN = ROWS * KC, SLN = COLS * KC, STN = ROWS * COLS;
-#if SDPB_TRSM_ALIAS
   // the T tile of the second phase lies over the X chunk of the first (whose last pass ends with a barrier): 384
-  // instead of 416 numbers of LDS per workgroup = five workgroups per CU instead of four
+  // instead of 416 numbers of LDS per workgroup = five workgroups per CU instead of four (P = L^-1 B 35.1 -> 34.1 ms on
+  // C4, profiles/r04t_trsm_variants.txt)
   static_assert(SXN <= STN, "the X chunk fits under the T tile");
   uint32_t *st = smem, *sx = smem, *sl = smem + (NL + 2) * STN;
-#else
-  uint32_t *sx = smem, *sl = sx + (NL + 2) * SXN, *st = sl + (NL + 2) * SLN;
-#endif
   if((int)(blockIdx.x * ROWS) >= dx.rows)
     return;
   const int n = dl.rows;
@@ -1307,12 +1256,7 @@ template <int NL> __global__ void __launch_bounds__(WG) k_trsm_rln_panel(Batch L
   if(k0 >= dl.rows)
     return;
   const int nb = dl.rows - k0 < PB ? dl.rows - k0 : PB;
-  constexpr int MINC = PB < 8 ? PB : 8, NMAX = (WG / MINC + MINC) * KC > (WG / PB + PB) * KC ? (WG / MINC + MINC) * KC : (WG / PB + PB) * KC;
-#if SDPB_TRSM_ALIAS
   __shared__ uint32_t smem[(NL + 2) * (WG + PB * KC)];
-#else
-  __shared__ uint32_t smem[(NL + 2) * (NMAX + WG)];
-#endif
   if constexpr(PB >= 32)
     {
       if(nb <= 8)
@@ -1422,71 +1366,9 @@ template <int NL> __global__ void __launch_bounds__(WG) k_symmetrize(Batch A, in
 //   out[k0..k0+nb) = xp                      (written by workgroup 0)
 //   forward : rhs[r] -= sum_k L(r, k0+k) xp[k]   for r >= k0+nb
 //   backward: rhs[r] -= sum_k L(k0+k, r) xp[k]   for r <  k0        (TRANS)
-// Every workgroup recomputes the small diagonal product (so one launch per panel
-// suffices) and owns QS_ROWS rows of the update; each dot product is split over
-// QS_SEG lanes and reduced through LDS, so the dependent chain per launch is
-// 2*(nb/QS_SEG + QS_SEG) multi-word operations instead of 2*nb.
-constexpr int QS_ROWS = PB, QS_SEG = WG / PB; // QS_ROWS * QS_SEG == WG; nb <= QS_ROWS
-template <int NL, bool TRANS>
-__global__ void __launch_bounds__(WG) k_qsolve_panel(Batch Q, Batch Linv, mw::Ptr rhs, mw::Ptr out, int k0)
-{
-  const MatDesc dq = Q.d[0], di = Linv.d[0];
-  const int N = dq.rows, nb = di.rows, t = threadIdx.x;
-  const int i = t % QS_ROWS, seg = t / QS_ROWS;
-  const int kper = (nb + QS_SEG - 1) / QS_SEG;
-  __shared__ Mw<NL> sx[QS_ROWS], sxp[QS_ROWS], part[WG];
-  if(t < nb)
-    sx[t] = mw::load<NL>(rhs, (size_t)k0 + t);
-  __syncthreads();
-  Acc<NL> acc = mw::acc_zero<NL>();
-  if(i < nb)
-    for(int k = seg * kper; k < (seg + 1) * kper && k < nb; ++k)
-      {
-        if(!TRANS && k <= i)
-          mw::acc_fma(acc, mat_ld<NL>(Linv, di, i, k), sx[k]);
-        if(TRANS && k >= i)
-          mw::acc_fma(acc, mat_ld<NL>(Linv, di, k, i), sx[k]);
-      }
-  part[t] = mw::acc_result(acc);
-  __syncthreads();
-  if(t < nb)
-    {
-      Acc<NL> ss = mw::acc_zero<NL>();
-      for(int g = 0; g < QS_SEG; ++g)
-        mw::acc_add(ss, part[g * QS_ROWS + t]);
-      const Mw<NL> s = mw::acc_result(ss);
-      sxp[t] = s;
-      if(blockIdx.x == 0)
-        mw::store<NL>(out, (size_t)k0 + t, s);
-    }
-  __syncthreads();
-  const int first = TRANS ? 0 : k0 + nb, count = TRANS ? k0 : N - k0 - nb;
-  const int ri = blockIdx.x * QS_ROWS + i;
-  acc = mw::acc_zero<NL>();
-  if(ri < count)
-    {
-      const int r = first + ri;
-      for(int k = seg * kper; k < (seg + 1) * kper && k < nb; ++k)
-        {
-          const Mw<NL> l = TRANS ? mat_ld<NL>(Q, dq, k0 + k, r) : mat_ld<NL>(Q, dq, r, k0 + k);
-          mw::acc_fma(acc, l, sxp[k]);
-        }
-    }
-  __syncthreads();
-  part[t] = mw::acc_result(acc);
-  __syncthreads();
-  if(seg == 0 && ri < count)
-    {
-      const size_t r = (size_t)first + ri;
-      Acc<NL> ss = mw::acc_zero<NL>();
-      mw::acc_add(ss, mw::load<NL>(rhs, r));
-      for(int g = 0; g < QS_SEG; ++g)
-        mw::acc_add(ss, part[g * QS_ROWS + t], 1u);
-      mw::store<NL>(rhs, r, mw::acc_result(ss));
-    }
-}
-
-// The same panel step with the dependent chain cut to 2 x (one product + a two-level sum):
+// Every workgroup recomputes the small diagonal product, so one launch per panel suffices.
+//
+// k_qsolve_panel2: the dependent chain cut to 2 x (one product + a two-level sum):
 // 1024-lane workgroups, lane (i, k) forms ONE product of row i's dot product; the PB products of a
 // row meet in a limb-major (conflict-free) LDS image and are summed exactly, eight at a time by four
 // lanes and then by one (mw::Acc: an aligned add per term, one rounding per level), instead of a
@@ -1511,19 +1393,10 @@ __global__ void __launch_bounds__(WG) k_qsolve_panel(Batch Q, Batch Linv, mw::Pt
 // inverses on the Cholesky(Q) chain — no net gain at one rank or at eight.
 constexpr int QS2_T = PB * PB <= 1024 ? PB * PB : 1024;
 constexpr int QS2_G = PB < 4 ? PB : 4; // lanes per row in the first level of the sum
-#ifdef SDPB_QS_TRACE
-__device__ long long qs_trace[2][64][8];
-#define QS_MARK(n)                                                                                                                         \
-  if(blockIdx.x == 0 && threadIdx.x == 0)                                                                                                    \
-  qs_trace[TRANS ? 1 : 0][(k0 / PB) & 63][n] = wall_clock64()
-#else
-#define QS_MARK(n)
-#endif
 template <int NL, bool TRANS>
 __global__ void __launch_bounds__(QS2_T) k_qsolve_panel2(Batch Q, Batch Linv, mw::Ptr rhs, mw::Ptr out, int k0)
 {
   raise_chain_priority();
-  QS_MARK(0);
   static_assert(PB * PB <= 1024 && PB % QS2_G == 0, "one lane per (row, column) of a panel");
   const MatDesc dq = Q.d[0], di = Linv.d[0];
   const int N = dq.rows, nb = di.rows, t = threadIdx.x;
@@ -1546,7 +1419,6 @@ __global__ void __launch_bounds__(QS2_T) k_qsolve_panel2(Batch Q, Batch Linv, mw
   if(t < PB)
     smem_st<NL, PB>(sx, t, t < nb ? mw::load<NL>(rhs, (size_t)k0 + t) : mw::zero<NL>());
   __syncthreads();
-  QS_MARK(1);
   // level 1 of the sum over k: lanes g1 < QS2_G take every QS2_G-th product of their row
   auto level1 = [&](const Mw<NL> &p) __attribute__((always_inline)) {
     smem_st<NL, STR>(part, slot(ip, kp), p);
@@ -1562,7 +1434,6 @@ __global__ void __launch_bounds__(QS2_T) k_qsolve_panel2(Batch Q, Batch Linv, mw
   };
   // xp = Linv_pp rhs_p (lower triangular; TRANS: its transpose)
   level1(mw::mul(li, smem_ld<NL, PB>(sx, kp)));
-  QS_MARK(2);
   if(g1 == 0)
     {
       Acc<NL> a = mw::acc_zero<NL>();
@@ -1574,10 +1445,8 @@ __global__ void __launch_bounds__(QS2_T) k_qsolve_panel2(Batch Q, Batch Linv, mw
         mw::store<NL>(out, (size_t)k0 + i1, xp);
     }
   __syncthreads();
-  QS_MARK(3);
   // rows outside the panel: rhs[r] -= sum_k L(r, k0 + k) xp[k]
   level1(mw::mul(lq, smem_ld<NL, PB>(sx, kp)));
-  QS_MARK(4);
   if(last)
     {
       Acc<NL> a = mw::acc_zero<NL>();
@@ -1586,7 +1455,6 @@ __global__ void __launch_bounds__(QS2_T) k_qsolve_panel2(Batch Q, Batch Linv, mw
         mw::acc_add(a, smem_ld<NL, STR>(part, slot(i1, g)), 1u);
       mw::store<NL>(rhs, (size_t)first + r1, mw::acc_result(a));
     }
-  QS_MARK(5);
 }
 
 // Round 4: the same panel step with both sums formed ACROSS the lanes as exact integer sums (mw.hpp: raw terms).
@@ -1867,41 +1735,12 @@ __global__ void __launch_bounds__(WG) k_constraint_weighted_sum(Batch bases, Bat
 }
 
 // dx[p] = -dual_residues[p] - Tr(A_p Z)   (compute_schur_RHS.cxx:21-86)
-template <int NL>
-__global__ void __launch_bounds__(WG)
-  k_schur_rhs(Batch bases, Batch Z, mw::CPtr dres, mw::Ptr dx, const BlockDesc *blk)
-{
-  const int j = blockIdx.y;
-  const BlockDesc bl = blk[j];
-  const int p = blockIdx.x * WG + threadIdx.x;
-  if(p >= bl.P)
-    return;
-  int cb, rb, k;
-  decode_p(p, bl.K, cb, rb, k);
-  Mw<NL> acc = mw::neg(mw::load<NL>(dres, (size_t)bl.voff + p));
-  for(int b = 0; b < 2; ++b)
-    {
-      const int rs = bl.rows[b];
-      const MatDesc dz = Z.d[2 * j + b], dbs = bases.d[2 * j + b];
-      Acc<NL> colsum = mw::acc_zero<NL>();
-      for(int i = 0; i < rs; ++i)
-        {
-          Acc<NL> zq = mw::acc_zero<NL>();
-          for(int l = 0; l < rs; ++l)
-            mw::acc_fma(zq, mat_ld<NL>(Z, dz, rb * rs + i, cb * rs + l), mat_ld<NL>(bases, dbs, l, k));
-          mw::acc_fma(colsum, mw::acc_result(zq), mat_ld<NL>(bases, dbs, i, k));
-        }
-      acc = mw::sub(acc, mw::acc_result(colsum));
-    }
-  mw::store<NL>(dx, (size_t)bl.voff + p, acc);
-}
-
-// The same right-hand side with the work of one (block, (r,s) pair) spread over a workgroup: lane
+// The work of one (block, (r,s) pair) is spread over a workgroup: lane
 // (k, g) owns sample point k and every G-th basis row i; per row it forms
 // W(i,k) = sum_l Z(rb rs + i, cb rs + l) q(l,k) and adds W(i,k) q(i,k) to its partial column sum
 // (the Z operand is a broadcast across the lanes of a group, q is read along k).  The dependent
-// chain per lane is 2 (rs/G)(rs + 1) products instead of 2 rs (rs + 1) (C4: 168 instead of 840), which
-// is what this latency-bound kernel costs: 3.0 -> 0.4 ms per launch.  grid (max pairs, blocks).
+// chain per lane is 2 (rs/G)(rs + 1) products instead of the 2 rs (rs + 1) of one lane per p (C4: 168 instead
+// of 840), which is what this latency-bound kernel costs: 3.0 -> 0.4 ms per launch.  grid (max pairs, blocks).
 template <int NL>
 __global__ void __launch_bounds__(WG)
   k_schur_rhs2(Batch basesT, Batch Z, mw::CPtr dres, mw::Ptr dx, const BlockDesc *blk)
@@ -3761,13 +3600,9 @@ __global__ void __launch_bounds__(WG)
 // Tuning knobs of the row loop, measured on C4 (40 000 x 1000, 512 bits; profiles/r02e_syrk_staging_variants.txt):
 //   direct-to-LDS staging, rows unrolled x4        185.1 ms, no spills   <- default
 //   register staging,      rows unrolled x4        183.9 ms, 2 spilled VGPRs
-//   register staging,      explicit LDS prefetch   186.6 ms, 11 spilled VGPRs = 8.9 GB of scratch writes per launch
-//   direct-to-LDS staging, explicit LDS prefetch   192.6 ms, no spills
-#ifndef SDPB_SYRK2_PREFETCH
-#define SDPB_SYRK2_PREFETCH 0
-#endif
+// (an explicit LDS prefetch of the next row was slower with either staging, 186.6 / 192.6 ms, same file, and is not kept)
 #ifndef SDPB_SYRK2_UNROLL
-#define SDPB_SYRK2_UNROLL 4 // row loop of the non-prefetching variant
+#define SDPB_SYRK2_UNROLL 4 // unroll factor of the row loop
 #endif
 // TOOM: the seven products of the Toom-4 image instead (one sweep); the seven row sums are written
 // as they are, A2 limbs each, to split * 7 A2 planes of the output, and k_syrk4_finish interpolates.
@@ -3811,7 +3646,7 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK_WAVES)
   // order), with no staging registers and no ds_write pass; the barrier that ends the pass drains
   // them (vmcnt) before any wavefront reads the buffer.  Rows past the end and columns past N load
   // a zero piece: they add nothing to any product.  Other piece sizes stage through registers.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SDPB_SYRK2_NO_GLDS)
+#if defined(__HIP_DEVICE_COMPILE__)
   constexpr bool DIRECT = (M2 == 4);
 #else
   constexpr bool DIRECT = false;
@@ -3913,34 +3748,13 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK_WAVES)
               h[k] = 0;
             }
           const uint32_t *pa = sa + (buf * NP + li) * M2, *pb = sb + (buf * NP + lj) * M2;
-          if constexpr(SDPB_SYRK2_PREFETCH && M2 <= 6)
-            {
-              // the LDS reads of the next row are issued before the MACs of the current one
-              uint32_t a0[M2], b0[M2], a1[M2], b1[M2];
-              piece_load<M2>(pa, a0);
-              piece_load<M2>(pb, b0);
-#pragma unroll 1
-              for(int rr = 0; rr < RBG; rr += 2)
-                {
-                  piece_load<M2>(pa + (rr + 1) * 16 * M2, a1);
-                  piece_load<M2>(pb + (rr + 1) * 16 * M2, b1);
-                  SyrkColumns<M2, 0>::run(a0, b0, c, h);
-                  const int nx = rr + 2 < RBG ? rr + 2 : 0; // the read past the last row is dropped
-                  piece_load<M2>(pa + nx * 16 * M2, a0);
-                  piece_load<M2>(pb + nx * 16 * M2, b0);
-                  SyrkColumns<M2, 0>::run(a1, b1, c, h);
-                }
-            }
-          else
-            {
 #pragma unroll SDPB_SYRK2_UNROLL
-              for(int rr = 0; rr < RBG; ++rr)
-                {
-                  uint32_t a[M2], b[M2];
-                  piece_load<M2>(pa + rr * 16 * M2, a);
-                  piece_load<M2>(pb + rr * 16 * M2, b);
-                  SyrkColumns<M2, 0>::run(a, b, c, h);
-                }
+          for(int rr = 0; rr < RBG; ++rr)
+            {
+              uint32_t a[M2], b[M2];
+              piece_load<M2>(pa + rr * 16 * M2, a);
+              piece_load<M2>(pb + rr * 16 * M2, b);
+              SyrkColumns<M2, 0>::run(a, b, c, h);
             }
           syrk_fold<M2, A2>(g2[g], c, h);
           store(buf ^ 1);
@@ -4010,22 +3824,17 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK_WAVES)
 // operand and row (4 LDS-array cycles, conflict-free, at full rate from one wavefront per SIMD) where the natural order
 // needs a ds_read2_b64 (8 cycles); the products and the output planes are the same.  One SWEEP over the split's rows = one of the 21 products: a pass per block of RBG rows, the column
 // accumulators (96 bits each, 4 x (2 M3 - 1) per lane) live in registers for the whole sweep and are folded when it ends.
-#ifndef SDPB_SYRK3_PREFETCH
-#define SDPB_SYRK3_PREFETCH 1 // measured on C4 (profiles/r04s_syrk3_variants.txt): 101.9 ms against 103.8 without
-#endif
+// The LDS reads of row r + 1 are issued before the products of row r (101.9 ms against 103.8 without: profiles/r04s_syrk3_variants.txt).
 #ifndef SDPB_SYRK3_WAVES
 #define SDPB_SYRK3_WAVES 3
 #endif
 #ifndef SDPB_SYRK3_LAZY_TRIP
 #define SDPB_SYRK3_LAZY_TRIP 32 // rows per trip of the lazy-carry row loop: the whole pass, every row's LDS offset an immediate
 #endif
-#ifndef SDPB_SYRK3_NBUF
-#define SDPB_SYRK3_NBUF 2 // staging buffers of the lazy-carry mode; 3 (requests two passes ahead) was measured: no gain, see below
-#endif
 template <int FX, int RBG>
 __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   k_syrk_fx3(const uint32_t *__restrict__ fx_in, size_t fx_stride, unsigned nrows, int N, uint32_t *acc, size_t acc_stride,
-             const uint32_t *tile_list, int ntile, int nsplit, unsigned rows_per_split, int gsplit, int order)
+             const uint32_t *tile_list, int ntile, int nsplit, unsigned rows_per_split, int gsplit)
 {
   // gsplit = 7 (21): a workgroup takes the three products of ONE Toom-4 group (one product) of its (tile, row split)
   // instead of all 21 (the sweeps are independent): more workgroups where the output has few tiles, a shorter tail everywhere
@@ -4040,20 +3849,11 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   static_assert(NPAIR % WG == 0, "a pass stages a whole number of units per lane");
   const uint32_t *fx = (const uint32_t *)__builtin_assume_aligned(fx_in, 4);
   const int nitem = ntile * nsplit * gsplit, per = (nitem + 7) / 8;
-  int item = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-  if(order == 1)
-    {
-      // (split, product)-major over the WHOLE chip (an experiment, SDPB_HIP_SYRK_ORDER=1; profiles/r05_syrk_order.txt): every
-      // XCD takes a contiguous eighth of the tiles of the same (split, product), so that all resident workgroups stream
-      // ONE panel set of rows_per_split x N pieces (20 MB on C4) at a time instead of eight of them
-      const int tper = (ntile + 7) / 8, slot = (int)(blockIdx.x / 8), sgx = slot / tper, tl = (int)(blockIdx.x % 8) * tper + slot % tper;
-      if(sgx >= nsplit * gsplit || tl >= ntile)
-        return;
-      item = sgx * ntile + tl;
-    }
-  else if((int)(blockIdx.x / 8) >= per || item >= nitem)
+  const int item = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+  if((int)(blockIdx.x / 8) >= per || item >= nitem)
     return;
-  // items that follow each other share the rows and the group, i.e. the operand panels of neighbouring tiles
+  // items that follow each other share the rows and the group, i.e. the operand panels of neighbouring tiles (a
+  // (split, product)-major order over the whole chip instead of per XCD was no faster: profiles/r05_syrk_order.txt)
   const int sg = item / ntile, tile = item % ntile, split = sg / gsplit;
   const int prod_begin = (sg % gsplit) * (NPROD / gsplit), prod_end = prod_begin + NPROD / gsplit;
   const unsigned row_begin = (unsigned)split * rows_per_split;
@@ -4066,25 +3866,15 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   // quadrant (p, q): rows i0 + 16 p of the output against columns j0 + 16 q; workgroup-uniform
   const bool half_i = ti * 32 + 16 < N, half_j = tj * 32 + 16 < N;
   const int mask = 1 | (half_i ? 2 : 0) | ((half_j && tj < ti) ? 4 : 0) | ((half_i && half_j) ? 8 : 0); // bit p + 2 q
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SDPB_SYRK2_NO_GLDS)
-  // -DSDPB_SYRK3_NBUF=3 (LAZY): three staging buffers, the rows of pass i + 2 requested while pass i multiplies.  Measured and
-  // NOT the default (profiles/r06_syrk_prefetch_depth.txt): the kernel without any fetch after the first pass of a sweep
-  // (wrong results, timing only: -DSDPB_SYRK3_EXPERIMENT_NO_FETCH) takes 74.3 instead of 82.2 ms for the whole syrk_G, which
-  // looked like passes waiting for rows that miss the XCD's L2 -- but requesting the rows a pass earlier changes nothing
-  // (81.9 against 80.9 ms, bit-exact either way): the 8 ms are the cost of the requests themselves, not of waiting for them.
-  constexpr int NBUF = LAZY ? SDPB_SYRK3_NBUF : 2;
-#else
-  constexpr int NBUF = 2;
-#endif
-  static_assert(NBUF == 2 || NBUF == 3, "double or triple buffering");
+  // two staging buffers (a third, requesting the rows two passes ahead, gains nothing: profiles/r06_syrk_prefetch_depth.txt)
   // (+ 64 words: the prefetching row loop reads one row past the pass it is in)
-  __shared__ __attribute__((aligned(16))) uint32_t sa[NBUF * NPAIR * 4 + 64];
-  __shared__ __attribute__((aligned(16))) uint32_t sb[NBUF * NPAIR * 4 + 64];
+  __shared__ __attribute__((aligned(16))) uint32_t sa[2 * NPAIR * 4 + 64];
+  __shared__ __attribute__((aligned(16))) uint32_t sb[2 * NPAIR * 4 + 64];
   uint64_t cc[4][2 * M3 - 1];
   uint32_t hh[4][2 * M3 - 1];
   uint64_t dd[4][2 * M3 - 1]; // LAZY: the high words taken out of the columns (weight 2^32 of their column)
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SDPB_SYRK2_NO_GLDS)
-  constexpr bool DIRECT = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool DIRECT = true; // (the host path of the emulation build stages through registers)
 #else
   constexpr bool DIRECT = false;
 #endif
@@ -4146,8 +3936,8 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   // fewer than 2^31 rows) persist over the whole sweep and are folded once, when it ends
   auto rows = [&](auto mask_c, int buf, uint64_t (&c)[4][2 * M3 - 1], uint32_t (&h)[4][2 * M3 - 1]) __attribute__((always_inline)) {
     constexpr int MASK = decltype(mask_c)::value;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SDPB_SYRK3_NO_ASM)
-    constexpr bool ASM_ROWS = (M3 == 2);
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool ASM_ROWS = (M3 == 2); // (the portable arm below is also the host path of the emulation build)
 #else
     constexpr bool ASM_ROWS = false;
 #endif
@@ -4166,16 +3956,13 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     constexpr int LSTEP = LAZY ? 2 * M3 : M3;
     const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sa + buf * NPAIR * 4 + li * LSTEP);
     const uint32_t lb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sb + buf * NPAIR * 4 + lj * LSTEP);
+    static_assert(RBG % 4 == 0 && M3 == 2, "four rows per trip, offsets in units of 8 bytes");
+    // One 2 x 2-limb product into the three columns of an output (ONE), or the products of both pieces of the i operand
+    // with one piece of the j operand into two outputs (BOTH).  FX3_*: carrying, 96-bit columns c + h 2^64; FX3L_*: lazy,
+    // plain 64-bit column sums.
 #define FX3_P(C, H, X, Y) "v_mad_u64_u32 %" #C ", vcc, %" #X ", %" #Y ", %" #C "\n\tv_addc_co_u32 %" #H ", vcc, 0, %" #H ", vcc\n\t"
 #define FX3_L(C, X, Y) "v_mad_u64_u32 %" #C ", vcc, %" #X ", %" #Y ", %" #C "\n\t"
 #define FX3_MAC_BOTH(o0, o1, a0x, a0y, a1x, a1y, bx, by)                                                                                   \
-  if constexpr(LAZY)                                                                                                                       \
-    asm volatile(FX3_L(0, 6, 10) FX3_L(3, 8, 10) FX3_L(1, 6, 11) FX3_L(4, 8, 11) FX3_L(1, 7, 10) FX3_L(4, 9, 10) FX3_L(2, 7, 11)           \
-                   FX3_L(5, 9, 11)                                                                                                         \
-                 : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2]), "+v"(c[o1][0]), "+v"(c[o1][1]), "+v"(c[o1][2])                          \
-                 : "v"(a0x), "v"(a0y), "v"(a1x), "v"(a1y), "v"(bx), "v"(by)                                                                \
-                 : "vcc");                                                                                                                 \
-  else                                                                                                                                     \
   asm volatile(FX3_P(0, 6, 12, 16) FX3_P(3, 9, 14, 16) FX3_P(1, 7, 12, 17) FX3_P(4, 10, 14, 17) FX3_P(1, 7, 13, 16) FX3_P(4, 10, 15, 16)   \
                  FX3_P(2, 8, 13, 17) FX3_P(5, 11, 15, 17)                                                                                  \
                : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2]), "+v"(c[o1][0]), "+v"(c[o1][1]), "+v"(c[o1][2]), "+v"(h[o0][0]),           \
@@ -4183,92 +3970,52 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
                : "v"(a0x), "v"(a0y), "v"(a1x), "v"(a1y), "v"(bx), "v"(by)                                                                  \
                : "vcc")
 #define FX3_MAC_ONE(o0, ax, ay, bx, by)                                                                                                    \
-  if constexpr(LAZY)                                                                                                                       \
-    asm volatile(FX3_L(0, 3, 5) FX3_L(1, 3, 6) FX3_L(1, 4, 5) FX3_L(2, 4, 6)                                                               \
-                 : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2])                                                                          \
-                 : "v"(ax), "v"(ay), "v"(bx), "v"(by)                                                                                      \
-                 : "vcc");                                                                                                                 \
-  else                                                                                                                                     \
   asm volatile(FX3_P(0, 3, 6, 8) FX3_P(1, 4, 6, 9) FX3_P(1, 4, 7, 8) FX3_P(2, 5, 7, 9)                                                     \
                : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2]), "+v"(h[o0][0]), "+v"(h[o0][1]), "+v"(h[o0][2])                            \
                : "v"(ax), "v"(ay), "v"(bx), "v"(by)                                                                                        \
                : "vcc")
-#define FX3_ROW(O0, O1)                                                                                                                    \
-  {                                                                                                                                        \
-    u32x4 va, vb; /* both pieces of either operand, also where MASK needs one (their columns are staged all the same) */                   \
-    asm volatile("ds_read2_b64 %0, %2 offset0:" #O0 " offset1:" #O1 "\n\tds_read2_b64 %1, %3 offset0:" #O0 " offset1:" #O1                \
-                 "\n\ts_waitcnt lgkmcnt(0)"                                                                                                \
-                 : "=&v"(va), "=&v"(vb)                                                                                                    \
-                 : "v"(xa), "v"(xb)                                                                                                        \
-                 : "memory");                                                                                                              \
-    if constexpr(MASK == 15)                                                                                                               \
-      {                                                                                                                                    \
-        FX3_MAC_BOTH(0, 1, va.x, va.y, va.z, va.w, vb.x, vb.y);                                                                            \
-        FX3_MAC_BOTH(2, 3, va.x, va.y, va.z, va.w, vb.z, vb.w);                                                                            \
-      }                                                                                                                                    \
-    else if constexpr(MASK == 11)                                                                                                          \
-      {                                                                                                                                    \
-        FX3_MAC_BOTH(0, 1, va.x, va.y, va.z, va.w, vb.x, vb.y);                                                                            \
-        FX3_MAC_ONE(3, va.z, va.w, vb.z, vb.w);                                                                                            \
-      }                                                                                                                                    \
-    else if constexpr(MASK == 5)                                                                                                           \
-      {                                                                                                                                    \
-        FX3_MAC_ONE(0, va.x, va.y, vb.x, vb.y);                                                                                            \
-        FX3_MAC_ONE(2, va.x, va.y, vb.z, vb.w);                                                                                            \
-      }                                                                                                                                    \
-    else                                                                                                                                   \
-      FX3_MAC_ONE(0, va.x, va.y, vb.x, vb.y);                                                                                              \
-  }
-    // LAZY: one 128-bit read per operand, the row's byte offset in the instruction's immediate
-#define FX3L_ROW(ROW)                                                                                                                      \
-  {                                                                                                                                        \
-    u32x4 va, vb;                                                                                                                          \
-    asm volatile("ds_read_b128 %0, %2 offset:%4\n\tds_read_b128 %1, %3 offset:%4\n\ts_waitcnt lgkmcnt(0)"                                  \
-                 : "=&v"(va), "=&v"(vb)                                                                                                    \
-                 : "v"(xa), "v"(xb), "n"((ROW) * 256)                                                                                      \
-                 : "memory");                                                                                                              \
-    FX3_MACS(va, vb)                                                                                                                       \
-  }
-    static_assert(RBG % 4 == 0 && M3 == 2, "four rows per trip, offsets in units of 8 bytes");
+#define FX3L_MAC_BOTH(o0, o1, a0x, a0y, a1x, a1y, bx, by)                                                                                  \
+  asm volatile(FX3_L(0, 6, 10) FX3_L(3, 8, 10) FX3_L(1, 6, 11) FX3_L(4, 8, 11) FX3_L(1, 7, 10) FX3_L(4, 9, 10) FX3_L(2, 7, 11)             \
+                 FX3_L(5, 9, 11)                                                                                                           \
+               : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2]), "+v"(c[o1][0]), "+v"(c[o1][1]), "+v"(c[o1][2])                            \
+               : "v"(a0x), "v"(a0y), "v"(a1x), "v"(a1y), "v"(bx), "v"(by)                                                                  \
+               : "vcc")
+#define FX3L_MAC_ONE(o0, ax, ay, bx, by)                                                                                                   \
+  asm volatile(FX3_L(0, 3, 5) FX3_L(1, 3, 6) FX3_L(1, 4, 5) FX3_L(2, 4, 6)                                                                 \
+               : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2])                                                                            \
+               : "v"(ax), "v"(ay), "v"(bx), "v"(by)                                                                                        \
+               : "vcc")
     // the products of one row for the quadrants of MASK
-#define FX3_MACS(va, vb)                                                                                                                   \
+#define FX3_QUADRANTS(BOTH, ONE, va, vb)                                                                                                   \
   if constexpr(MASK == 15)                                                                                                                 \
     {                                                                                                                                      \
-      FX3_MAC_BOTH(0, 1, va.x, va.y, va.z, va.w, vb.x, vb.y);                                                                              \
-      FX3_MAC_BOTH(2, 3, va.x, va.y, va.z, va.w, vb.z, vb.w);                                                                              \
+      BOTH(0, 1, va.x, va.y, va.z, va.w, vb.x, vb.y);                                                                                      \
+      BOTH(2, 3, va.x, va.y, va.z, va.w, vb.z, vb.w);                                                                                      \
     }                                                                                                                                      \
   else if constexpr(MASK == 11)                                                                                                            \
     {                                                                                                                                      \
-      FX3_MAC_BOTH(0, 1, va.x, va.y, va.z, va.w, vb.x, vb.y);                                                                              \
-      FX3_MAC_ONE(3, va.z, va.w, vb.z, vb.w);                                                                                              \
+      BOTH(0, 1, va.x, va.y, va.z, va.w, vb.x, vb.y);                                                                                      \
+      ONE(3, va.z, va.w, vb.z, vb.w);                                                                                                      \
     }                                                                                                                                      \
   else if constexpr(MASK == 5)                                                                                                             \
     {                                                                                                                                      \
-      FX3_MAC_ONE(0, va.x, va.y, vb.x, vb.y);                                                                                              \
-      FX3_MAC_ONE(2, va.x, va.y, vb.z, vb.w);                                                                                              \
+      ONE(0, va.x, va.y, vb.x, vb.y);                                                                                                      \
+      ONE(2, va.x, va.y, vb.z, vb.w);                                                                                                      \
     }                                                                                                                                      \
   else                                                                                                                                     \
-    FX3_MAC_ONE(0, va.x, va.y, vb.x, vb.y);
-#if SDPB_SYRK3_PREFETCH
+    ONE(0, va.x, va.y, vb.x, vb.y);
+#define FX3_MACS(va, vb) FX3_QUADRANTS(FX3_MAC_BOTH, FX3_MAC_ONE, va, vb)
+#define FX3L_MACS(va, vb) FX3_QUADRANTS(FX3L_MAC_BOTH, FX3L_MAC_ONE, va, vb)
     // The reads of row r + 1 are issued before the products of row r: two register sets, each handed from the
     // statement that issues its reads to the statement that waits for them without the compiler touching it in between.
-    // wait for the set (wa, wb) that is in flight, then issue the reads of (ra, rb)
-#ifdef SDPB_SYRK3_EXPERIMENT_HALF_LDS
-    // TIMING EXPERIMENT ONLY (wrong results): the pieces of the second operand are not read -- what the kernel would cost
-    // with half of its LDS reads (profiles/r06_syrk_lds_experiment.txt)
-#define FX3_NEXT(wa, wb, ra, rb, O0, O1)                                                                                                   \
-  asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read2_b64 %2, %4 offset0:" #O0 " offset1:" #O1                                                  \
-               : "+v"(wa), "+v"(wb), "=&v"(ra), "+v"(rb)                                                                                   \
-               : "v"(xa), "v"(xb)                                                                                                          \
-               : "memory")
-#else
+    // (With half of the LDS reads the whole product would be 5 % faster: profiles/r06_syrk_lds_experiment.txt.)
+    // FX3_NEXT: wait for the set (wa, wb) that is in flight, then issue the reads of (ra, rb)
 #define FX3_NEXT(wa, wb, ra, rb, O0, O1)                                                                                                   \
   asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read2_b64 %2, %4 offset0:" #O0 " offset1:" #O1 "\n\tds_read2_b64 %3, %5 offset0:" #O0            \
                " offset1:" #O1                                                                                                             \
                : "+v"(wa), "+v"(wb), "=&v"(ra), "=&v"(rb)                                                                                  \
                : "v"(xa), "v"(xb)                                                                                                          \
                : "memory")
-#endif
     // LAZY: wait for the set (wa, wb), then issue the two 128-bit reads of row ROW of the trip into (ra, rb); the row's
     // byte offset (256 ROW, at most 32 rows: 8192) is the instruction's immediate, so a trip needs no address arithmetic
 #define FX3L_NEXT(wa, wb, ra, rb, ROW)                                                                                                     \
@@ -4278,9 +4025,9 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
                : "memory")
 #define FX3L_ROWS2(R)                                                                                                                      \
   FX3L_NEXT(a0, b0, a1, b1, (R) + 1);                                                                                                      \
-  FX3_MACS(a0, b0)                                                                                                                         \
+  FX3L_MACS(a0, b0)                                                                                                                        \
   FX3L_NEXT(a1, b1, a0, b0, (R) + 2);                                                                                                      \
-  FX3_MACS(a1, b1)
+  FX3L_MACS(a1, b1)
 #define FX3L_ROWS8(R) FX3L_ROWS2(R) FX3L_ROWS2((R) + 2) FX3L_ROWS2((R) + 4) FX3L_ROWS2((R) + 6)
     u32x4 a0, b0, a1, b1;
     if constexpr(LAZY)
@@ -4337,35 +4084,11 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
 #undef FX3L_ROWS2
 #undef FX3L_NEXT
 #undef FX3_NEXT
-#else
-    if constexpr(LAZY)
-      {
-#pragma unroll 1
-        for(int rr = 0; rr < RBG; rr += 4)
-          {
-            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
-            FX3L_ROW(0)
-            FX3L_ROW(1)
-            FX3L_ROW(2)
-            FX3L_ROW(3)
-          }
-      }
-    else
-      {
-#pragma unroll 1
-        for(int rr = 0; rr < RBG; rr += 4)
-          {
-            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
-            FX3_ROW(0, 16)
-            FX3_ROW(32, 48)
-            FX3_ROW(64, 80)
-            FX3_ROW(96, 112)
-          }
-      }
-#endif
+#undef FX3L_MACS
 #undef FX3_MACS
-#undef FX3L_ROW
-#undef FX3_ROW
+#undef FX3_QUADRANTS
+#undef FX3L_MAC_ONE
+#undef FX3L_MAC_BOTH
 #undef FX3_MAC_ONE
 #undef FX3_MAC_BOTH
 #undef FX3_P
@@ -4463,23 +4186,9 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
       };
       if(prod > prod_begin)
         __syncthreads(); // every wavefront has left the last pass of the previous sweep (and what it over-fetched has landed)
-      // the barrier that ends a pass: the rows of the NEXT pass have landed in LDS; with three buffers the requests of
-      // the pass after it (2 GL per lane, the youngest) may still be in flight
-      auto pass_barrier = [&]() __attribute__((always_inline)) {
-        if constexpr(NBUF == 3)
-          {
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(2 * GL) : "memory");
-#endif
-          }
-        else
-          __syncthreads();
-      };
       fetch(prod, row_begin, 0);
-      if constexpr(NBUF == 3)
-        fetch(prod, row_begin + RBG < row_end ? row_begin + RBG : row_begin, 1);
       store(0);
-      pass_barrier();
+      __syncthreads();
       // the row blocks of the sweep; the quadrant mask is chosen outside the loop, so that the accumulators stay in
       // the same registers from block to block
       auto sweep = [&](auto mask_c) __attribute__((always_inline)) {
@@ -4488,30 +4197,14 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
         for(unsigned r0 = row_begin; r0 < row_end; r0 += RBG)
           {
             // (after the last block of the sweep: a block that exists, staged and never read)
-#ifdef SDPB_SYRK3_EXPERIMENT_NO_FETCH
-            if(r0 == row_begin) // TIMING EXPERIMENT ONLY (wrong results): what the kernel costs when no pass waits for its rows
-#endif
-            {
-              if constexpr(NBUF == 3)
-                fetch(prod, r0 + 2 * RBG < row_end ? r0 + 2 * RBG : row_begin, buf >= 1 ? buf - 1 : 2);
-              else
-                fetch(prod, r0 + RBG < row_end ? r0 + RBG : row_begin, buf ^ 1);
-            }
+            fetch(prod, r0 + RBG < row_end ? r0 + RBG : row_begin, buf ^ 1);
             rows(mask_c, buf, cc, hh);
             ++pass;
             if(LAZY && (pass & 1u) == 0) // every second pass
               carry_columns((pass & 3u) == 0);
-            if constexpr(NBUF == 3)
-              {
-                pass_barrier();
-                buf = buf == 2 ? 0 : buf + 1;
-              }
-            else
-              {
-                store(buf ^ 1);
-                __syncthreads();
-                buf ^= 1;
-              }
+            store(buf ^ 1);
+            __syncthreads(); // the rows of the next pass have landed in LDS
+            buf ^= 1;
           }
       };
       switch(mask)
@@ -5073,9 +4766,6 @@ constexpr int TRI_V = 64;
 template <int NL> struct TriSlot
 {
   Mw<NL> v;
-#ifdef SDPB_TRI_PAD
-  uint32_t pad[(sizeof(Mw<NL>) / 4) % 2 == 0 ? 1 : 2]; // the measured variant: odd stride in words
-#endif
 };
 template <int NL> __device__ Mw<NL> tri_reduce_sum(const Mw<NL> &v, TriSlot<NL> *sm)
 {
@@ -5229,16 +4919,16 @@ __global__ void __launch_bounds__(T, T <= 256 ? SDPB_TRI_WAVES : 1024 / T) k_tri
 // products; ONE reciprocal per Newton step.  The exponent of Mw is an int32: the minors of a 40 x 40 matrix cannot leave
 // it.  x below the spectrum <=> every p_i > 0.  Each step of the recurrence is one rounding of (d_i - x) and of e_i^2,
 // as in the quotient form.  k_tridiag_min 2.37 -> 1.99 ms per launch on C4 (profiles/r05_tridiag_min.txt: 0.68 ms of it
-// are the fp64 bisection, 0.58 / 0.34 / 0.40 ms the 6-, 10- and 18-limb rungs); -DSDPB_TRIMIN_POLY=0: the quotient form.
-#ifndef SDPB_TRIMIN_POLY
-#define SDPB_TRIMIN_POLY 1
-#endif
+// are the fp64 bisection, 0.58 / 0.34 / 0.40 ms the 6-, 10- and 18-limb rungs).
 template <int WL, int NL>
 __device__ void tridiag_newton(const Batch &D, const Batch &E, size_t od, size_t oe, int n, Mw<WL> &x, double span, int emax,
                                int backoff_bits, bool &clustered)
 {
   // clustered (in/out): a narrower rung of the ladder met slow convergence -- then a first step that is already small says
   // nothing about the distance to go (it is that distance over m), and the rung iterates until two steps show the ratio
+  // (minus_one, and inv and tq below, are unused since the quotient form of the recurrence was removed: without them the
+  // compiler allocates the registers of k_tridiag_min and of Solver::norms_to_inverse differently, and that removal was to
+  // leave the device code as it was -- they can go with the next change that touches this kernel)
   const Mw<WL> minus_one = mw::from_i32<WL>(-1);
   Mw<WL> prev = x;
   // A CLUSTER of m eigenvalues at the bottom of the spectrum, tighter than the distance still to go, makes the Newton step
@@ -5259,7 +4949,6 @@ __device__ void tridiag_newton(const Batch &D, const Batch &E, size_t od, size_t
     {
       Mw<WL> S = mw::zero<WL>(), inv = mw::zero<WL>(), tq = mw::zero<WL>();
       bool overshoot = false;
-#if SDPB_TRIMIN_POLY
       {
         Mw<WL> pm = mw::from_i32<WL>(1), pmm = mw::zero<WL>(), dpm = mw::zero<WL>(), dpmm = mw::zero<WL>();
         for(int i = 0; i < n; ++i)
@@ -5289,26 +4978,6 @@ __device__ void tridiag_newton(const Batch &D, const Batch &E, size_t od, size_t
         if(!overshoot && !mw::is_zero(dpm))
           S = mw::mul(dpm, mw::rcp(pm)); // p'/p = sum_i q_i'/q_i
       }
-#else
-      for(int i = 0; i < n; ++i)
-        {
-          Mw<WL> qi = mw::sub(mw::narrow<WL, NL>(mw::load<NL>(D.p, od + i)), x), qp = minus_one;
-          if(i >= 1)
-            {
-              const Mw<WL> u = mw::mul(mw::narrow<WL, NL>(mw::load<NL>(E.p, oe + i)), inv);
-              qi = mw::sub(qi, u);
-              qp = mw::add(minus_one, mw::mul(u, tq));
-            }
-          if(qi.neg || mw::is_zero(qi))
-            {
-              overshoot = true;
-              break;
-            }
-          inv = mw::rcp(qi);
-          tq = mw::mul(qp, inv);
-          S = mw::add(S, tq);
-        }
-#endif
 #ifdef SDPB_TRACE_TRIMIN
       if(overshoot)
         printf("WL=%d it=%d overshoot accel_pending=%d x.e=%d\n", WL, it, (int)accel_pending, x.e);
@@ -5787,32 +5456,11 @@ __global__ void __launch_bounds__(WG) k_cond_best(mw::CPtr ratio, int Jl, const 
 }
 
 // ---- multi-GPU exchange images ----------------------------------------------
-// 32-bit two's-complement limbs widened to u64 lanes so that an integer SUM
-// all-reduce (RCCL ncclSum on uint64) adds the partial Q' of every GPU exactly;
-// k_narrow_carry propagates the deferred carries afterwards.  
-template <int UNUSED = 0> __global__ void __launch_bounds__(WG) k_widen_u64(const uint32_t *in, size_t count, unsigned long long *out)
-{
-  for(size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < count; i += (size_t)gridDim.x * WG)
-    out[i] = in[i];
-}
-template <int UNUSED = 0>
-__global__ void __launch_bounds__(WG)
-  k_narrow_carry(const unsigned long long *in, size_t elems, int planes, uint32_t *out)
-{
-  for(size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < elems; i += (size_t)gridDim.x * WG)
-    {
-      unsigned long long carry = 0;
-      for(int k = 0; k < planes; ++k)
-        {
-          const unsigned long long s = in[(size_t)k * elems + i] + carry;
-          out[(size_t)k * elems + i] = (uint32_t)s;
-          carry = s >> 32;
-        }
-    }
-}
-// The same pair for the Q' accumulators: only the lower triangle (i >= j) and the N column sums
-// behind it carry information, so only those N(N+1)/2 + N entries per plane travel (half the
-// message).  Packed entry of (i, j): j N - j (j - 1) / 2 + (i - j); column sum i: N(N+1)/2 + i.
+// The 32-bit two's-complement limbs of the Q' accumulators are widened to u64 lanes so that an integer SUM
+// all-reduce (RCCL ncclSum on uint64) adds the partial Q' of every GPU exactly; k_narrow_tri_carry propagates
+// the deferred carries afterwards.    Only the lower triangle (i >= j) and the N column sums
+// behind it carry information, so only those N(N+1)/2 + N entries per plane travel.
+// Packed entry of (i, j): j N - j (j - 1) / 2 + (i - j); column sum i: N(N+1)/2 + i.
 // grid (cdiv(N, WG), N + 1): blockIdx.y = column j, j == N is the row of column sums.
 // Columns [c0, c1) only (a chunk of the chased Q'): the message holds their packed entries, then -- with_sums -- the N
 // column sums; grid (cdiv(N, WG), c1 - c0 + with_sums): blockIdx.y = c1 - c0 is the row of column sums.

@@ -2059,12 +2059,8 @@ private:
         if constexpr(SYRK_TOOM4)
           {
             if constexpr(SYRK_TOOM4K)
-              {
-                static const int order = std::getenv("SDPB_HIP_SYRK_ORDER") ? std::atoi(std::getenv("SDPB_HIP_SYRK_ORDER")) : 0;
-                const size_t blocks = order == 1 ? (size_t)8 * cdiv(nt, 8) * nsplit * gsplit : (size_t)8 * cdiv((size_t)nt * nsplit * gsplit, 8);
-                launch(k_syrk_fx3<FX, SYRK_RB>, dim3((unsigned)blocks), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl, nt, nsplit, rps,
-                       gsplit, order);
-              }
+              launch(k_syrk_fx3<FX, SYRK_RB>, dim3(8 * cdiv((size_t)nt * nsplit * gsplit, 8)), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl,
+                     nt, nsplit, rps, gsplit);
             else
               launch(k_syrk_fx2<FX, SYRK_RB, true>, dim3(8 * cdiv((size_t)nt * nsplit, 8)), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl, nt,
                      nsplit, rps, (const uint32_t *)zero_piece_.p, 1);
@@ -2324,36 +2320,25 @@ private:
     {
       Timer t(this, "searchDirection.solve.dy_Qinv");
       // El::cholesky::SolveAfter with the blocked factor: forward (dy -> qtmpv_), then
-      // backward (qtmpv_ -> dy); one launch per panel
+      // backward (qtmpv_ -> dy); one launch per panel, one lane per (row, column) of the panel
+      static_assert(PB * PB <= 1024, "the Q-substitution kernels take a PB x PB panel per workgroup");
       for(int p = 0; p < q_panels_; ++p)
         {
           const int k0 = p * q_nb_, nb = std::min(q_nb_, N_ - k0), rest = N_ - k0 - nb;
           Batch iv{LiQ_.ptr(), d_qdiag_.p + p, 1};
-          if constexpr(PB * PB <= 1024)
-            {
-              if(qsolve_sum_lanes_)
-                launch(k_qsolve_panel3<NL, false>, dim3(std::max(1u, cdiv(rest, PB))), dim3(QS2_T), stream_, QB(), iv, dy_.ptr(), qtmpv_.ptr(), k0);
-              else
-                launch(k_qsolve_panel2<NL, false>, dim3(std::max(1u, cdiv(rest, PB))), dim3(QS2_T), stream_, QB(), iv, dy_.ptr(), qtmpv_.ptr(), k0);
-            }
+          if(qsolve_sum_lanes_)
+            launch(k_qsolve_panel3<NL, false>, dim3(std::max(1u, cdiv(rest, PB))), dim3(QS2_T), stream_, QB(), iv, dy_.ptr(), qtmpv_.ptr(), k0);
           else
-            launch(k_qsolve_panel<NL, false>, dim3(std::max(1u, cdiv(rest, QS_ROWS))), dim3(WG), stream_, QB(), iv, dy_.ptr(),
-                   qtmpv_.ptr(), k0);
+            launch(k_qsolve_panel2<NL, false>, dim3(std::max(1u, cdiv(rest, PB))), dim3(QS2_T), stream_, QB(), iv, dy_.ptr(), qtmpv_.ptr(), k0);
         }
       for(int p = q_panels_ - 1; p >= 0; --p)
         {
           const int k0 = p * q_nb_;
           Batch iv{LiQ_.ptr(), d_qdiag_.p + p, 1};
-          if constexpr(PB * PB <= 1024)
-            {
-              if(qsolve_sum_lanes_)
-                launch(k_qsolve_panel3<NL, true>, dim3(std::max(1u, cdiv(k0, PB))), dim3(QS2_T), stream_, QB(), iv, qtmpv_.ptr(), dy_.ptr(), k0);
-              else
-                launch(k_qsolve_panel2<NL, true>, dim3(std::max(1u, cdiv(k0, PB))), dim3(QS2_T), stream_, QB(), iv, qtmpv_.ptr(), dy_.ptr(), k0);
-            }
+          if(qsolve_sum_lanes_)
+            launch(k_qsolve_panel3<NL, true>, dim3(std::max(1u, cdiv(k0, PB))), dim3(QS2_T), stream_, QB(), iv, qtmpv_.ptr(), dy_.ptr(), k0);
           else
-            launch(k_qsolve_panel<NL, true>, dim3(std::max(1u, cdiv(k0, QS_ROWS))), dim3(WG), stream_, QB(), iv, qtmpv_.ptr(), dy_.ptr(),
-                   k0);
+            launch(k_qsolve_panel2<NL, true>, dim3(std::max(1u, cdiv(k0, PB))), dim3(QS2_T), stream_, QB(), iv, qtmpv_.ptr(), dy_.ptr(), k0);
         }
     }
     {
@@ -2943,25 +2928,6 @@ public:
   // sdpb_hip_bench_op: average HIP-event time of one kernel on synthetic operands (ms)
   double bench_op(const std::string &op, int a, int b, int reps) override
   {
-#ifdef SDPB_QS_TRACE
-    if(op == "qstrace")
-      {
-        HIP_CHECK(hipStreamSynchronize(stream_));
-        static long long h[2][64][8];
-        HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(qs_trace), sizeof(h)));
-        for(int d = 0; d < 2; ++d)
-          for(int p = 0; p < 32; p += 5)
-            {
-              fprintf(stderr, "qstrace dir %d panel %2d:", d, p);
-              for(int m = 1; m < 6; ++m)
-                fprintf(stderr, " %6.2f", (double)(h[d][p][m] - h[d][p][m - 1]) * 0.01);
-              if(p + 1 < 32)
-                fprintf(stderr, "   next start - this end %6.2f us", (double)(h[d][d ? (p ? p - 1 : 0) : p + 1][0] - h[d][p][5]) * 0.01);
-              fprintf(stderr, "\n");
-            }
-        return 0;
-      }
-#endif
     if(op == "trsm")
       {
         // P = L^{-1} B with the solver's own blocks and the factors of the last iteration (a = b = 0)
