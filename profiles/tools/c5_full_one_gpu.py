@@ -1,7 +1,7 @@
 """FULL C5 (BASELINE.json config 5: J = 8192 blocks of m = 6, K = 2, N = 2048, --precision 1024: P_tot = 344 064 rows) on the ONE
 288-GB GPU of the box.  What made it fit (round 6): the fixed-point image of P' -- 237 GB for all rows at once -- is built one
-INPUT WINDOW of rows at a time in a bounded buffer and every window's exact product is added into Q' (Solver::q_window,
-syrk_G_windows; the reference's input_window_split_factor, BigInt_Shared_Memory_Syrk_Context.cxx:70-110,172-186,
+INPUT WINDOW of rows at a time in a bounded buffer and every window's exact product is added into Q' (FxSyrk::q_window,
+FxSyrk::G_windows; the reference's input_window_split_factor, BigInt_Shared_Memory_Syrk_Context.cxx:70-110,172-186,
 bigint_syrk_blas.cxx:239-285).  B and P (2 x 98.7 GB) stay resident.
 
 No oracle can hold this SDP (the J = 1024 slice costs it 40 min per iteration and 45 GB).  What is checked instead:

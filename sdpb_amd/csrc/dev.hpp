@@ -12,6 +12,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #ifndef HIP_KERNEL_NAME
@@ -154,4 +155,32 @@ template <int NL> std::vector<mw::Mw<NL>> download(const DevArray &a, size_t fir
 }
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// kernel launches of the solver whose entry point is running on this thread (round-4 advisor: the figure in timers_json
+// was a process-wide counter): launch() adds to the counter a LaunchScope has installed for the calling thread -- the
+// iteration entry points of a Solver install their own -- and to a thread's stray counter otherwise.  The latency floor
+// of a small SDP is launches x dispatch cost; bench.py reports launches per iteration next to the host synchronisations.
+inline unsigned long long *&launch_sink()
+{
+  static thread_local unsigned long long stray = 0;
+  static thread_local unsigned long long *sink = &stray;
+  return sink;
+}
+struct LaunchScope
+{
+  unsigned long long *prev;
+  explicit LaunchScope(unsigned long long *mine) : prev(launch_sink()) { launch_sink() = mine; }
+  ~LaunchScope() { launch_sink() = prev; }
+  LaunchScope(const LaunchScope &) = delete;
+  LaunchScope &operator=(const LaunchScope &) = delete;
+};
+template <class... KArgs, class... Args>
+inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t stream, Args &&...args)
+{
+  if(grid.x == 0 || grid.y == 0 || grid.z == 0)
+    return;
+  ++*launch_sink();
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, std::forward<Args>(args)...);
+  HIP_CHECK(hipGetLastError());
+}
 } // namespace sdpb

@@ -2910,45 +2910,6 @@ __global__ void __launch_bounds__(WG) k_fx_colsum_final(const uint32_t *partial,
     acc[(size_t)k * acc_stride + (size_t)N * N + col] = w[k];
 }
 
-// Lower-triangle tiles of an N x N output, enumerated super-block by super-block
-// (8x8 tiles) so that consecutive entries share operand panels.
-// split_col > 0: the tiles that hold outputs of the columns [0, split_col) come first (super-block order inside each
-// group), *count_left = how many they are; the tiles that hold outputs of the columns [split_col, N) follow -- the two
-// launches of the chunked Q' take the two parts of the list.  Where split_col is not a multiple of the tile edge, the
-// tiles of the straddling tile column are in BOTH parts (their products are computed twice; each part's finishing
-// kernel reads only its own columns).
-// edge: 16, or 32 for k_syrk_fx3 (super-blocks of 4x4 tiles then cover the same 128 columns)
-inline std::vector<uint32_t> syrk_tile_order(int N, int split_col = 0, int *count_left = nullptr, int edge = 16)
-{
-  int SB = edge == 16 ? 8 : 4;
-  if(const char *env = std::getenv("SDPB_HIP_SYRK_SB")) // tuning knob: super-block edge in tiles
-    SB = std::max(1, std::atoi(env));
-  const int tiles = (N + edge - 1) / edge, nsb = (tiles + SB - 1) / SB;
-  std::vector<uint32_t> all;
-  for(int bi = 0; bi < nsb; ++bi)
-    for(int bj = 0; bj <= bi; ++bj)
-      for(int ti = bi * SB; ti < std::min(tiles, (bi + 1) * SB); ++ti)
-        for(int tj = bj * SB; tj < std::min(tiles, (bj + 1) * SB); ++tj)
-          if(tj <= ti)
-            all.push_back((uint32_t)ti << 16 | (uint32_t)tj);
-  if(split_col <= 0)
-    {
-      if(count_left)
-        *count_left = (int)all.size();
-      return all;
-    }
-  std::vector<uint32_t> out;
-  for(uint32_t t : all)
-    if((int)(t & 0xffffu) * edge < split_col)
-      out.push_back(t);
-  if(count_left)
-    *count_left = (int)out.size();
-  for(uint32_t t : all)
-    if(((int)(t & 0xffffu) + 1) * edge > split_col)
-      out.push_back(t);
-  return out;
-}
-
 // all 2M-1 columns of one row's M x M limb product into column accumulators that
 // persist across rows: c[K] (64 bits) + h[K] 2^64 collects column K
 template <int M, int K> struct SyrkColumns
@@ -3037,7 +2998,7 @@ MW_HD void syrk_rows(const uint32_t (&sa)[PL * RB * 16], const uint32_t (&sb)[PL
 // images) their output planes hold only the tiles of the launch: element (i, j) of tile t of the launch's tile list at
 //   t E E + (i - E ti) + (j - E tj) E        (E = syrk_tile_edge<FX>(), plane stride = ntile E E words)
 // -- half the words of the N x N planes of rounds 1-4 (only the lower triangle has tiles), and a launch over a SUBSET of
-// the tiles needs planes for that subset only: Solver::syrk_G walks the tile list in chunks whose planes fit a memory
+// the tiles needs planes for that subset only: FxSyrk::G (syrk_stage.hpp) walks the tile list in chunks whose planes fit a memory
 // budget (the reference bounds the same stage by looping over output windows: bigint_syrk_blas.cxx:200-220,
 // BigInt_Shared_Memory_Syrk_Context.cxx:149-215, --maxSharedMemory).  The finishing kernels run one lane per packed
 // word, find (i, j) through the tile list and drop what lies outside the lower triangle, N, or the columns [col0, col1).
@@ -3065,37 +3026,6 @@ template <int E> MW_HD bool syrk_packed_decode(size_t pidx, const uint32_t *tile
 #define SDPB_SYRK_WAVES (FX <= 16 ? 3 : 2) // 3 waves x 168 VGPRs hold the staging registers of the pipeline without spills
 #endif
 template <int FX> constexpr int syrk_waves_per_simd();
-// nsplit in [1, 32]: fewest splits within 2% of the best occupancy of the last round.  (Up to 16 until round 4: with
-// N = 100 the output has 28 tiles, and 16 splits filled 448 of the chip's 768 workgroup slots — C3's product took
-// 2.08 ms at 8 splits, 3.8 at 4, 15 at 1: profiles/r04k_syrk_row_splits.txt; the row floor of 64 passes per split
-// still applies.)
-// max_rows > 0 (k_syrk_fx3): at least so many splits that one has no more rows than that.  The workgroups of an XCD that
-// stream the same operand panels drift apart by no more than a split's rows, so short splits are what lets them meet in
-// that XCD's L2: on C4 (profiles/r04x_syrk3_fetch_vs_splits.txt) FETCH_SIZE per launch 99.7 M KB with 2 splits of 20 000
-// rows, 78 with 8, 49 with 16 (2500 rows: same kernel time), 22 with 32 (+ 3.5 % time: the finishing kernel adds 32 x 105 planes).
-constexpr int SYRK_MAX_SPLITS = 32;
-inline int syrk_row_splits(int ntile, unsigned nrows, int slots, int rb, unsigned max_rows = 0)
-{
-  if(const char *env = std::getenv("SDPB_HIP_SYRK_SPLITS")) // tests force the split path on small inputs
-    return std::max(1, std::min(SYRK_MAX_SPLITS, std::atoi(env)));
-  int smin = 1;
-  while(max_rows && smin < SYRK_MAX_SPLITS && nrows / (unsigned)smin > max_rows && nrows / (unsigned)(smin + 1) >= 64u * (unsigned)rb)
-    ++smin;
-  int best = smin;
-  double best_eff = 0;
-  for(int s = smin; s <= SYRK_MAX_SPLITS; ++s)
-    {
-      if(s > smin && nrows / (unsigned)s < 64u * (unsigned)rb)
-        break;
-      const double items = (double)ntile * s, rounds = std::ceil(items / slots), eff = items / (rounds * slots);
-      if(eff > best_eff + 0.02)
-        {
-          best = s;
-          best_eff = eff;
-        }
-    }
-  return best;
-}
 template <int FX, int RB>
 __global__ void __launch_bounds__(WG, SDPB_SYRK_WAVES)
   k_syrk_fx(const uint32_t *fx, size_t fx_stride, unsigned nrows, int N, uint32_t *acc, size_t acc_stride, const uint32_t *tile_list,

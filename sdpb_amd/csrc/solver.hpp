@@ -8,6 +8,7 @@
 // HIP kernel launch (kernels.hpp).
 #pragma once
 #include "kernels.hpp"
+#include "syrk_stage.hpp"
 #include "mw_host.hpp"
 
 #include <algorithm>
@@ -207,34 +208,6 @@ public:
   virtual std::string op_min_eigenvalue(int n, const char *A_colmajor) = 0;
 };
 
-// kernel launches of the solver whose entry point is running on this thread (round-4 advisor: the figure in timers_json
-// was a process-wide counter): launch() adds to the counter a LaunchScope has installed for the calling thread -- the
-// iteration entry points of a Solver install their own -- and to a thread's stray counter otherwise.  The latency floor
-// of a small SDP is launches x dispatch cost; bench.py reports launches per iteration next to the host synchronisations.
-inline unsigned long long *&launch_sink()
-{
-  static thread_local unsigned long long stray = 0;
-  static thread_local unsigned long long *sink = &stray;
-  return sink;
-}
-struct LaunchScope
-{
-  unsigned long long *prev;
-  explicit LaunchScope(unsigned long long *mine) : prev(launch_sink()) { launch_sink() = mine; }
-  ~LaunchScope() { launch_sink() = prev; }
-  LaunchScope(const LaunchScope &) = delete;
-  LaunchScope &operator=(const LaunchScope &) = delete;
-};
-template <class... KArgs, class... Args>
-inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t stream, Args &&...args)
-{
-  if(grid.x == 0 || grid.y == 0 || grid.z == 0)
-    return;
-  ++*launch_sink();
-  hipLaunchKernelGGL(kernel, grid, block, 0, stream, std::forward<Args>(args)...);
-  HIP_CHECK(hipGetLastError());
-}
-
 inline void split_numbers(const char *txt, std::vector<std::pair<const char *, const char *>> &out)
 {
   out.clear();
@@ -258,23 +231,7 @@ template <int NL> class Solver : public SolverBase
   using M = Mw<NL>;
   static constexpr int FX = fx_limbs<NL>(); // 32 (NL - 2) = GMP's rounded precision 64 (l - 1) (compute_Q.cxx:107), or the next multiple of four limbs
   static_assert(FX <= NL, "the image is cut from an NL-limb product");
-  static constexpr int ACCW = 2 * FX + 2;
-  static constexpr bool SYRK_TOOM4 = fx_toom4<FX>();         // seven (FX/4)^2 products per row pair (k_syrk_fx2<.., true> + k_syrk4_finish)
-  static constexpr bool SYRK_TOOM4K = fx_toom4k<FX>();       // ... and one Karatsuba level below them: 21 (FX/8)^2 products (k_syrk_fx3)
-  static constexpr bool SYRK_TOOM5K = fx_toom5k<FX>();       // Toom-5 x Karatsuba on 28-bit limbs, lazy carries: 27 products of 2 x 2 limbs (k_syrk_fx3 in lazy mode + k_syrk5_finish)
-  static constexpr int SYRK_NPROD = fx_nprod<FX>();          // products per row pair of k_syrk_fx3
-  static constexpr int SYRK_EDGE = syrk_tile_edge<FX>();     // output tile of the syrk kernel in use
-  static constexpr unsigned SYRK_SPLIT_ROWS = SYRK_TOOM4K ? 2560u : 0u; // rows per row split of k_syrk_fx3 at most (kernels.hpp: syrk_row_splits)
-  static constexpr bool SYRK_TWO_LEVEL = fx_two_level<FX>() || SYRK_TOOM4; // piece-major image: nine (two Karatsuba levels) or seven pieces
-  static constexpr int SYRK_PART_PLANES = SYRK_TOOM4K ? SYRK_NPROD * fx_part_limbs<FX>() : SYRK_TOOM4 ? 7 * (2 * (FX / 4) + 1) : ACCW; // planes one row split writes
-  // words per column of the bias terms of the signed evaluation points (k_fx_colsum4_final / k_fx_colsum5_final), of a slice's column sums
-  static constexpr size_t TOOMU_WORDS = SYRK_TOOM5K ? (size_t)3 * T5_Z : (size_t)2 * (2 * (FX / 4) + 2);
-  static constexpr size_t COLSUM_WORDS = SYRK_TOOM5K ? 25 : FX + 8; // 5 x 5, or 2 (FX/2 + 2) / 4 (FX/4 + 2) limbs per column and slice
-  // rows per LDS chunk: k_syrk_fx2 stages one piece group of 32 rows per pass; k_syrk_fx 3 FX/2 planes x RB rows
-#ifndef SDPB_SYRK2_RBG
-#define SDPB_SYRK2_RBG (FX >= 32 ? 16 : 32)
-#endif
-  static constexpr int SYRK_RB = SYRK_TWO_LEVEL ? SDPB_SYRK2_RBG : (FX <= 24 ? 16 : 8);
+  using Syrk = FxSyrk<FX>; // the exact product Q' = P'^T P' (syrk_stage.hpp): its formats, budgets, plans, buffers and launches
 
   // ---- problem shape -------------------------------------------------------
   int precision_, J_, N_, rank_, world_;
@@ -310,8 +267,6 @@ template <int NL> class Solver : public SolverBase
   DevArray LiX_, LiY_, LiS_, LiQ_, qtmpv_; // inverted diagonal blocks of the Cholesky factors
   DevArray part2_; // partial sums of the column norms (the Q chain may run beside the predictor, which uses part_)
   DevArray b_, y_, dy_, rp_, norms_, invnorms_, Q_, invdQ_, part_, red_, red2_, lam_, lam2_, ratio_, scal_;
-  DevBuf<uint32_t> fx_, acc_, syrk_tiles_, colsum_partial_, syrk_part_, toomU_;
-  DevBuf<uint32_t> acc2_; // partial G of the input windows after the first (image in several row chunks: q_window())
   // P = L^{-1} B with the trailing updates as fixed-point tile dot products (kernels.hpp: k_td_image_L, k_trsm_rlt_panel_td):
   // images of the tiles of every L_j below its diagonal blocks, their row exponents and limb sums, tile offsets per block
   bool use_td_ = false;
@@ -319,8 +274,8 @@ template <int NL> class Solver : public SolverBase
   DevBuf<uint32_t> td_img_, td_sum_;
   DevBuf<int32_t> td_exp_;
   int td_max_tiles_ = 0;
-  int num_cus_ = 256;
-  unsigned colsum_slices_ = 1;
+  int num_cus_;
+  Syrk syrk_; // the iteration's stage: all local rows of P' x N
   DevBuf<double> eigF_, eigF2_;
   DevBuf<unsigned long long> acc64_;
   DevBuf<int> flags_; // [0..2Jl) chol fail per psd (X) matrix, then Q fail, Q diag fail
@@ -361,12 +316,12 @@ template <int NL> class Solver : public SolverBase
   // multiplied, finished, reduced over the ranks and restored first; panels [0, chase_hA_) are factored on the side
   // streams while the main stream multiplies the right chunk
   bool q_chase_ = false;
-  int chase_hA_ = 0, chase_cA_ = 0, chase_ntileA_ = 0, chase_ntile_ = 0;
+  int chase_hA_ = 0, chase_cA_ = 0;
   hipEvent_t ev_chunk_ = nullptr, ev_syrk2_ = nullptr, ev_syrk3_ = nullptr;
   bool syrk_events2_pending_ = false;
   long xc_broadcast_calls_ = 0;
   double xc_broadcast_bytes_ = 0;
-  DevBuf<uint32_t> resbuf_, xgather_, zero_piece_; // zero_piece_: what k_syrk_fx2 stages for rows/columns outside the image
+  DevBuf<uint32_t> resbuf_, xgather_;
   std::vector<M> res_host_ = std::vector<M>(R_COUNT);
   uint32_t xw_host_[X_EXTRA] = {0xffffffffu, 0, 0, 0, 0, 0, 0};
   std::unique_ptr<Comm> comm_;
@@ -421,7 +376,6 @@ template <int NL> class Solver : public SolverBase
   std::chrono::steady_clock::time_point start_time_;
   bool started_ = false;
   std::atomic<int> stop_requested_{0};
-  size_t fx_stride_ = 0, acc_stride_ = 0;
 
   // ---- parameters (Solver_Parameters.hxx:13-30) --------------------------------
   M duality_gap_threshold_, primal_error_threshold_, dual_error_threshold_, initial_matrix_scale_primal_,
@@ -473,18 +427,10 @@ template <int NL> class Solver : public SolverBase
 public:
   Solver(int precision_bits, const std::vector<int> &dims, const std::vector<int> &num_points, int N, int rank, int world,
          const std::vector<long long> &block_costs = {})
-      : precision_(precision_bits), J_((int)dims.size()), N_(N), rank_(rank), world_(world), dims_(dims), npts_(num_points)
+      : precision_(precision_bits), J_((int)dims.size()), N_(N), rank_(rank), world_(world), dims_(dims), npts_(num_points),
+        num_cus_(device_cus(N, (int)dims.size())), syrk_(num_cus_)
   {
-    if(N <= 0 || J_ <= 0)
-      throw SolverError(4, "sdpb_hip_create: need at least one block and N >= 1");
     owner_ = plan_block_owners(dims, num_points, N, world, block_costs);
-    {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      HIP_CHECK(hipGetDevice(&dev));
-      HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-      num_cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
     HIP_CHECK(hipStreamCreate(&stream_main_));
     stream_ = stream_main_;
     {
@@ -539,6 +485,16 @@ public:
     HIP_CHECK(hipEventCreateWithFlags(&ev_chunk_, hipEventDisableTiming));
     build_layout();
     set_default_params();
+  }
+  static int device_cus(int N, int J) // the argument check comes first: bad arguments throw without touching the device
+  {
+    if(N <= 0 || J <= 0)
+      throw SolverError(4, "sdpb_hip_create: need at least one block and N >= 1");
+    int dev = 0;
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
   ~Solver() override
   {
@@ -595,9 +551,9 @@ public:
   // the product (output window: the rest); 0 = the default plan
   void set_max_shared_memory(unsigned long long bytes) override
   {
-    max_shared_bytes_ = (size_t)bytes;
+    syrk_.set_max_shared_memory((size_t)bytes);
     HIP_CHECK(hipStreamSynchronize(stream_main_));
-    plan_syrk_part();
+    prepare_syrk();
   }
   // bytes per array class on this rank + the plan of the syrk's partial planes
   std::string memory_plan_json() override
@@ -615,11 +571,11 @@ public:
         b += x;
       return b;
     };
-    const unsigned tiles = cdiv(N_, SYRK_EDGE);
-    const int ntile = q_chase_ ? std::max(chase_ntileA_, chase_ntile_ - chase_ntileA_) : (int)(tiles * (tiles + 1) / 2);
-    const SyrkPlan pl = syrk_plan(ntile, qwin_.chunk_rows, syrk_part_budget_words());
-    const SyrkPlan unbounded = syrk_plan(ntile, (unsigned)Ptot_, 0);
-    const size_t tile_words = (size_t)SYRK_PART_PLANES * SYRK_EDGE * SYRK_EDGE;
+    const QWindow &qwin = syrk_.win;
+    const SyrkRecord &rec = syrk_.record();
+    const size_t part_budget = syrk_.syrk_part_budget_words();
+    const SyrkPlan pl = syrk_.syrk_plan(syrk_.plan_tiles(), qwin.chunk_rows, part_budget);
+    const SyrkPlan unbounded = syrk_.syrk_plan(syrk_.plan_tiles(), (unsigned)Ptot_, 0);
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     std::ostringstream o;
@@ -629,34 +585,32 @@ public:
       << ", \"bases_and_pairings\": " << da({&bases_, &basesT_, &scaled_, &E_, &Et_, &T_, &YQ_, &AX_, &AY_})
       << ", \"schur_blocks\": " << da({&S_, &LiS_})
       << ", \"B\": " << da({&BT_}) << ", \"P\": " << da({&PT_})
-      << ", \"P_fixed_point_image\": " << fx_.n * sizeof(uint32_t)
-      << ", \"Q\": " << da({&Q_, &LiQ_}) + db({acc_.n * sizeof(uint32_t), acc2_.n * sizeof(uint32_t), acc64_.n * sizeof(unsigned long long), qpanel_msg_.n * sizeof(uint32_t)})
-      << ", \"syrk_partial_planes\": " << syrk_part_.n * sizeof(uint32_t)
+      << ", \"P_fixed_point_image\": " << syrk_.image.n * sizeof(uint32_t)
+      << ", \"Q\": " << da({&Q_, &LiQ_}) + db({syrk_.acc.n * sizeof(uint32_t), syrk_.acc2.n * sizeof(uint32_t), acc64_.n * sizeof(unsigned long long), qpanel_msg_.n * sizeof(uint32_t)})
+      << ", \"syrk_partial_planes\": " << syrk_.part.n * sizeof(uint32_t)
       << ", \"vectors_and_small\": "
       << da({&c_, &x_, &dx_, &dres_, &invdS_, &invdX_, &invdY_, &eigD_, &eigE_, &eigD2_, &eigE2_, &b_, &y_, &dy_, &rp_, &norms_, &invnorms_, &invdQ_,
              &qtmpv_, &part_, &part2_, &red_, &red2_, &lam_, &lam2_, &ratio_, &scal_, &cmby_})
-           + db({colsum_partial_.n * sizeof(uint32_t), toomU_.n * sizeof(uint32_t), xgather_.n * sizeof(uint32_t)})
-      << "}, \"syrk\": {\"tile_edge\": " << SYRK_EDGE << ", \"tiles\": " << pl.ntile << ", \"chunks\": " << pl.nchunk
+           + db({syrk_.colsum_partial.n * sizeof(uint32_t), syrk_.toomU.n * sizeof(uint32_t), xgather_.n * sizeof(uint32_t)})
+      << "}, \"syrk\": {\"tile_edge\": " << Syrk::SYRK_EDGE << ", \"tiles\": " << pl.ntile << ", \"chunks\": " << pl.nchunk
       << ", \"tiles_per_chunk\": " << pl.chunk_tiles << ", \"row_splits\": " << pl.nsplit_first
-      << ", \"rows_per_split\": " << (pl.nsplit_first ? cdiv(qwin_.chunk_rows, pl.nsplit_first) : 0) << ", \"planes_per_split\": " << SYRK_PART_PLANES
+      << ", \"rows_per_split\": " << (pl.nsplit_first ? cdiv(qwin.chunk_rows, pl.nsplit_first) : 0) << ", \"planes_per_split\": " << Syrk::SYRK_PART_PLANES
       << ", \"partial_bytes\": " << pl.part_words * sizeof(uint32_t) << ", \"partial_bytes_unbounded\": " << unbounded.part_words * sizeof(uint32_t)
       << ", \"partial_bytes_full_square_layout\": "
-      << (size_t)unbounded.nsplit_first * SYRK_PART_PLANES * ((size_t)N_ * N_ + N_) * sizeof(uint32_t) * (unbounded.uses_part ? 1 : 0)
-      << ", \"budget_bytes\": " << syrk_part_budget_words() * sizeof(uint32_t) << ", \"budget_source\": \""
-      << (std::getenv("SDPB_HIP_SYRK_PART_BYTES") ? "SDPB_HIP_SYRK_PART_BYTES" : max_shared_bytes_ ? "maxSharedMemory" : "device")
-      << "\", \"bound_exceeded_min_chunk\": " << (pl.uses_part && pl.part_words > syrk_part_budget_words() ? "true" : "false")
-      << ", \"min_chunk_bytes\": " << tile_words * sizeof(uint32_t) << "}"
+      << (size_t)unbounded.nsplit_first * Syrk::SYRK_PART_PLANES * ((size_t)N_ * N_ + N_) * sizeof(uint32_t) * (unbounded.uses_part ? 1 : 0)
+      << ", \"budget_bytes\": " << part_budget * sizeof(uint32_t) << ", \"budget_source\": \"" << syrk_.budget_source(false)
+      << "\", \"bound_exceeded_min_chunk\": " << (pl.uses_part && pl.part_words > part_budget ? "true" : "false")
+      << ", \"min_chunk_bytes\": " << Syrk::TILE_WORDS * sizeof(uint32_t) << "}"
       // the input window (BigInt_Shared_Memory_Syrk_Context.cxx:70-110: input_window_split_factor)
-      << ", \"image\": {\"image_chunks\": " << qwin_.chunks << ", \"rows_per_chunk\": " << qwin_.chunk_rows << ", \"rows\": " << Ptot_
-      << ", \"image_bytes\": " << qwin_.image_words * sizeof(uint32_t) << ", \"image_bytes_unbounded\": " << image_words_for(std::max<size_t>(Ptot_, 1), (size_t)N_) * sizeof(uint32_t)
-      << ", \"budget_bytes\": " << qwin_.budget_words * sizeof(uint32_t) << ", \"budget_source\": \""
-      << (std::getenv("SDPB_HIP_SYRK_IMAGE_BYTES") ? "SDPB_HIP_SYRK_IMAGE_BYTES" : max_shared_bytes_ ? "maxSharedMemory/2" : "device/2")
-      << "\", \"bound_exceeded_min_chunk\": " << (qwin_.bound_exceeded ? "true" : "false") << ", \"accumulator_bytes\": " << acc2_.n * sizeof(uint32_t)
-      << ", \"last_call_windows\": " << last_windows_ << "}"
-      << ", \"window_budget_bytes\": " << window_budget_words() * sizeof(uint32_t)
-      << ", \"last_syrk_call\": {\"tiles\": " << last_syrk_plan_.ntile << ", \"chunks\": " << last_syrk_plan_.nchunk
-      << ", \"tiles_per_chunk\": " << last_syrk_plan_.chunk_tiles << ", \"row_splits\": " << last_syrk_plan_.nsplit_first
-      << ", \"partial_bytes\": " << last_syrk_plan_.part_words * sizeof(uint32_t) << "}"
+      << ", \"image\": {\"image_chunks\": " << qwin.chunks << ", \"rows_per_chunk\": " << qwin.chunk_rows << ", \"rows\": " << Ptot_
+      << ", \"image_bytes\": " << qwin.image_words * sizeof(uint32_t) << ", \"image_bytes_unbounded\": " << Syrk::image_words_for(std::max<size_t>(Ptot_, 1), (size_t)N_) * sizeof(uint32_t)
+      << ", \"budget_bytes\": " << qwin.budget_words * sizeof(uint32_t) << ", \"budget_source\": \"" << syrk_.budget_source(true)
+      << "\", \"bound_exceeded_min_chunk\": " << (qwin.bound_exceeded ? "true" : "false") << ", \"accumulator_bytes\": " << syrk_.acc2.n * sizeof(uint32_t)
+      << ", \"last_call_windows\": " << rec.last_windows << "}"
+      << ", \"window_budget_bytes\": " << syrk_.window_budget_words() * sizeof(uint32_t)
+      << ", \"last_syrk_call\": {\"tiles\": " << rec.last_plan.ntile << ", \"chunks\": " << rec.last_plan.nchunk
+      << ", \"tiles_per_chunk\": " << rec.last_plan.chunk_tiles << ", \"row_splits\": " << rec.last_plan.nsplit_first
+      << ", \"partial_bytes\": " << rec.last_plan.part_words * sizeof(uint32_t) << "}"
       << ", \"device\": {\"free_bytes\": " << free_b << ", \"total_bytes\": " << total_b << "}}";
     return o.str();
   }
@@ -829,23 +783,13 @@ private:
             td_exp_.alloc(tiles * PB);
           }
       }
-    // (the fixed-point image of P' is planned last, with the partial planes: plan_syrk_part())
-    acc_stride_ = (size_t)N_ * N_ + N_; // N x N outputs + N column sums (k_fx_colsum)
-    acc_.alloc(acc_stride_ * ACCW);
-    if(SYRK_TOOM4)
-      toomU_.alloc(TOOMU_WORDS * N_);
-    colsum_slices_ = (unsigned)std::min<size_t>(128, std::max<size_t>(1, cdiv(Ptot_, 64)));
-    colsum_partial_.alloc((size_t)colsum_slices_ * COLSUM_WORDS * N_);
-    syrk_tiles_.upload(syrk_tile_order(N_, 0, nullptr, SYRK_EDGE));
+    // (the buffers of the exact product Q' = P'^T P' are planned last: prepare_syrk())
     if(world_ > 1)
-      {
-        acc64_.alloc(((size_t)N_ * (N_ + 1) / 2 + N_) * ACCW);
-      }
+      acc64_.alloc(((size_t)N_ * (N_ + 1) / 2 + N_) * Syrk::ACCW);
     flags_.alloc((size_t)2 * std::max(Jl_, 1) + 4);
     flags2_.alloc((size_t)2 * std::max(Jl_, 1));
     flags3_.alloc((size_t)std::max(Jl_, 1));
     resbuf_.alloc(RES_WORDS);
-    zero_piece_.alloc(64);
     if(world_ > 1)
       xgather_.alloc(std::max(RES_WORDS, (size_t)(NL + 1) * N_) * world_);
     if(const char *e = std::getenv("SDPB_HIP_PROFILE"))
@@ -892,63 +836,15 @@ private:
       bool want = false;
       if(const char *e = std::getenv("SDPB_HIP_Q_CHASE"))
         want = std::atoi(e) != 0;
-      const unsigned tiles = cdiv(N_, SYRK_EDGE);
-      chase_ntile_ = (int)(tiles * (tiles + 1) / 2);
       chase_hA_ = std::max(step, (panels / 2) / step * step);
       chase_cA_ = PB * chase_hA_;
       q_chase_ = want && !dist_cholq_ && !(overlap_syrk_ && world_ == 1) && chase_hA_ < panels && chase_cA_ < N_; // the same decision on every rank
-      if(q_chase_)
-        {
-          {
-            // (where the chunk boundary is not a tile boundary the straddling tile column is in both parts of the list)
-            const std::vector<uint32_t> order = syrk_tile_order(N_, chase_cA_, &chase_ntileA_, SYRK_EDGE);
-            chase_ntile_ = (int)order.size();
-            syrk_tiles_.upload(order);
-          }
-        }
     }
-    {
-      // The two windows of the Q stage -- the fixed-point image of P' (input window) and the partial planes of the
-      // product (output window) -- are planned last and TOGETHER, against what is left of the device: everything else
-      // of this solver is allocated by now.  (The reference bounds the sum of its input and output residue windows by
-      // --maxSharedMemory the same way: BigInt_Shared_Memory_Syrk_Context.cxx:149-215.)  Reserve for what comes later
-      // (the exchange's buffers and RCCL's, operator scratch): 1/16 of the device + 1 GiB; never more than 1/8 of the
-      // device -- chunking costs nothing measurable while a chunk keeps thousands of workgroups
-      // (profiles/r05_syrk_chunks.txt, r06_image_chunks.txt), and ranks that share a GPU (tests) each see the memory
-      // the others have not taken yet.  SDPB_HIP_SYRK_IMAGE_BYTES / SDPB_HIP_SYRK_PART_BYTES /
-      // sdpb_hip_set_max_shared_memory override.
-      size_t free_b = 0, total_b = 0;
-      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-      const size_t reserve = total_b / 16 + ((size_t)1 << 30);
-      size_t b = free_b > reserve ? free_b - reserve : 0;
-      b = std::min(b, total_b / 8);
-      syrk_part_default_words_ = std::max<size_t>(b, (size_t)64 << 20) / sizeof(uint32_t);
-      plan_syrk_part();
-    }
+    // (where the chunk boundary of a chased Q' is not a tile boundary the straddling tile column is in both parts of the tile list)
+    prepare_syrk();
   }
-  // (re)size the image of P' (fx_, one input window) and syrk_part_ (one output window) for the iteration's syrk_G
-  // call(s) under the current budget
-  void plan_syrk_part()
-  {
-    qwin_ = q_window((unsigned)Ptot_, N_, /*one_chunk=*/q_chase_);
-    fx_stride_ = qwin_.stride;
-    if(fx_.n != qwin_.image_words)
-      image_alloc(fx_, qwin_.stride);
-    if(qwin_.chunks > 1 && acc2_.n != acc_stride_ * ACCW)
-      acc2_.alloc(acc_stride_ * ACCW);
-    const size_t budget = syrk_part_budget_words(qwin_.image_words);
-    size_t words = 0;
-    if(q_chase_)
-      words = std::max(syrk_plan(chase_ntileA_, qwin_.chunk_rows, budget).part_words,
-                       syrk_plan(chase_ntile_ - chase_ntileA_, qwin_.chunk_rows, budget).part_words);
-    else
-      {
-        const unsigned tiles = cdiv(N_, SYRK_EDGE);
-        words = syrk_plan((int)(tiles * (tiles + 1) / 2), qwin_.chunk_rows, budget).part_words;
-      }
-    if(words && syrk_part_.n != words)
-      syrk_part_.alloc(words);
-  }
+  // (re)size the buffers of the Q stage under the current budget: after everything else of this solver is allocated
+  void prepare_syrk() { syrk_.prepare(Ptot_, N_, stream_, /*one_chunk=*/q_chase_, q_chase_ ? chase_cA_ : 0); }
 
   void set_default_params()
   {
@@ -1023,12 +919,12 @@ public:
         first = false;
       }
     // dominant kernel: HIP-event time, launches, algorithmic bytes and limb MACs per launch
-    const double fx_bytes = (double)Ptot_ * N_ * (FX + 1) * 4.0, acc_bytes = (double)N_ * (N_ + 1) / 2 * ACCW * 4.0;
+    const double fx_bytes = (double)Ptot_ * N_ * (FX + 1) * 4.0, acc_bytes = (double)N_ * (N_ + 1) / 2 * Syrk::ACCW * 4.0;
     ss << (first ? "" : ", ") << "\"kernel.k_syrk_fx.ms\": " << syrk_kernel_ms_ << ", \"kernel.k_syrk_fx.launches\": " << syrk_launches_
        << ", \"kernel.k_syrk_fx.algorithmic_bytes\": " << (fx_bytes + acc_bytes)
        << ", \"kernel.k_syrk_fx.limb_macs\": "
-       << (double)Ptot_ * N_ * (N_ + 1) / 2 * FX * FX * (SYRK_TOOM5K ? 27.0 / 64 : SYRK_TOOM4K ? 21.0 / 64 : SYRK_TOOM4 ? 7.0 / 16 : SYRK_TWO_LEVEL ? 9.0 / 16 : 0.75) // executed: 21 (FX/8)^2, 7 or 9 (FX/4)^2, or 3 (FX/2)^2 per product
-       << ", \"kernel.k_syrk_fx.karatsuba_levels\": " << (SYRK_TOOM4 ? 0 : SYRK_TWO_LEVEL ? 2 : 1) << ", \"kernel.k_syrk_fx.toom4\": " << (SYRK_TOOM4 ? 1 : 0) << ", \"kernel.k_syrk_fx.toom4k\": " << (SYRK_TOOM4K ? 1 : 0) << ", \"kernel.k_syrk_fx.toom5k_lazy_carries\": " << (SYRK_TOOM5K ? 1 : 0)
+       << (double)Ptot_ * N_ * (N_ + 1) / 2 * FX * FX * (Syrk::SYRK_TOOM5K ? 27.0 / 64 : Syrk::SYRK_TOOM4K ? 21.0 / 64 : Syrk::SYRK_TOOM4 ? 7.0 / 16 : Syrk::SYRK_TWO_LEVEL ? 9.0 / 16 : 0.75) // executed: 21 (FX/8)^2, 7 or 9 (FX/4)^2, or 3 (FX/2)^2 per product
+       << ", \"kernel.k_syrk_fx.karatsuba_levels\": " << (Syrk::SYRK_TOOM4 ? 0 : Syrk::SYRK_TWO_LEVEL ? 2 : 1) << ", \"kernel.k_syrk_fx.toom4\": " << (Syrk::SYRK_TOOM4 ? 1 : 0) << ", \"kernel.k_syrk_fx.toom4k\": " << (Syrk::SYRK_TOOM4K ? 1 : 0) << ", \"kernel.k_syrk_fx.toom5k_lazy_carries\": " << (Syrk::SYRK_TOOM5K ? 1 : 0)
        << ", \"host_syncs\": " << host_syncs_ << ", \"launches\": " << launches_
        << ", \"iterations\": " << iteration_ << ", \"comm.world\": " << world_ << ", \"comm.ranks\": " << (comm_ ? comm_->ranks() : (world_ == 1 ? 1 : 0))
        << ", \"comm.owned_blocks\": " << Jl_ << ", \"comm.owned_rows\": " << Ptot_ << ", \"comm.allgather_calls\": " << xc_allgather_calls_
@@ -1735,8 +1631,10 @@ private:
       auto make_image = [&](size_t r0, unsigned rows) {
         const size_t n = (size_t)rows * N_;
         launch(k_normalize_fx<NL, FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, mw::offset(PT_.cptr(), r0 * (size_t)N_), n, N_, // one element per lane: streams at HBM rate
-               invnorms_.cptr(), fx_.p, fx_stride_);
+               invnorms_.cptr(), syrk_.image.p, syrk_.win.stride);
       };
+      uint32_t *const acc = syrk_.acc.p;
+      const size_t acc_stride = syrk_.acc_stride, acc_bytes = syrk_.acc.n * sizeof(uint32_t);
       if(cnt && q_chase_)
         make_image(0, (unsigned)Ptot_);
       int *qflags = flags_.p + 2 * std::max(Jl_, 1);
@@ -1744,8 +1642,8 @@ private:
       // unbias + un-normalise the columns [c0, c1) of the lower triangle into Q (check of the diagonal included)
       auto finish_Q_columns = [&](int c0, int c1) {
         const size_t idx0 = (size_t)c0 * N_, idx1 = (size_t)c1 * N_;
-        launch(k_syrk_unbias<FX>, dim3(cdiv(idx1 - idx0, WG)), dim3(WG), stream_, acc_.p, acc_stride_, N_, Ptot_global_, idx0, idx1);
-        launch(k_restore_Q<NL, FX>, dim3(cdiv(idx1 - idx0, WG)), dim3(WG), stream_, (const uint32_t *)acc_.p, acc_stride_, N_, norms_.cptr(),
+        launch(k_syrk_unbias<FX>, dim3(cdiv(idx1 - idx0, WG)), dim3(WG), stream_, acc, acc_stride, N_, Ptot_global_, idx0, idx1);
+        launch(k_restore_Q<NL, FX>, dim3(cdiv(idx1 - idx0, WG)), dim3(WG), stream_, (const uint32_t *)acc, acc_stride, N_, norms_.cptr(),
                Q_.ptr(), qflags + 1, idx0, idx1);
       };
       if(q_chase_)
@@ -1754,18 +1652,17 @@ private:
           // ranks, reduces) the right chunk, the side streams factor the panels of the left one -- half of the chain
           // of diagonal blocks, the part of Cholesky(Q) that no number of GPUs shortens, moves behind the product.
           // Every rank issues the same collectives in the same order (two all-reduces instead of one).
-          const uint32_t *tl = (const uint32_t *)syrk_tiles_.p;
           const int cA = chase_cA_;
           if(cnt)
             {
-              syrk_column_sums(fx_.p, fx_stride_, (unsigned)Ptot_, N_, acc_.p, acc_stride_, colsum_partial_.p, colsum_slices_, toomU_.p);
+              syrk_.column_sums(stream_);
               resolve_syrk_events();
               HIP_CHECK(hipEventRecord(ev_syrk0_, stream_));
-              syrk_G(fx_.p, fx_stride_, (unsigned)Ptot_, N_, acc_.p, acc_stride_, tl, syrk_part_, toomU_.p, chase_ntileA_, 0, cA);
+              syrk_.G(stream_, syrk_.left());
               HIP_CHECK(hipEventRecord(ev_syrk1_, stream_));
             }
           else
-            HIP_CHECK(hipMemsetAsync(acc_.p, 0, acc_.n * sizeof(uint32_t), stream_));
+            HIP_CHECK(hipMemsetAsync(acc, 0, acc_bytes, stream_));
           if(world_ > 1)
             reduce_Q_accumulators(0, cA, true);
           finish_Q_columns(0, cA);
@@ -1773,8 +1670,7 @@ private:
           if(cnt)
             {
               HIP_CHECK(hipEventRecord(ev_syrk2_, stream_));
-              syrk_G(fx_.p, fx_stride_, (unsigned)Ptot_, N_, acc_.p, acc_stride_, tl + chase_ntileA_, syrk_part_, toomU_.p,
-                     chase_ntile_ - chase_ntileA_, cA, N_);
+              syrk_.G(stream_, syrk_.right());
               HIP_CHECK(hipEventRecord(ev_syrk3_, stream_));
               syrk_events_pending_ = syrk_events2_pending_ = true;
             }
@@ -1789,16 +1685,15 @@ private:
           // HIP events on the launch stream bracket the dominant kernel (bench.py roofline); they are
           // read back lazily, after a later synchronisation point has passed them.  (With the image in several
           // input windows they also span the images and column sums of the windows after the first.)
-          syrk_G_windows(qwin_, (unsigned)Ptot_, N_, fx_, acc_.p, acc_stride_, acc2_, colsum_partial_.p, (const uint32_t *)syrk_tiles_.p, syrk_part_,
-                         toomU_.p, make_image, [&] {
-                           resolve_syrk_events();
-                           HIP_CHECK(hipEventRecord(ev_syrk0_, stream_));
-                         });
+          syrk_.G_windows(stream_, make_image, [&] {
+            resolve_syrk_events();
+            HIP_CHECK(hipEventRecord(ev_syrk0_, stream_));
+          });
           HIP_CHECK(hipEventRecord(ev_syrk1_, stream_));
           syrk_events_pending_ = true;
         }
       else
-        HIP_CHECK(hipMemsetAsync(acc_.p, 0, acc_.n * sizeof(uint32_t), stream_));
+        HIP_CHECK(hipMemsetAsync(acc, 0, acc_bytes, stream_));
       if(world_ > 1)
         reduce_Q_accumulators();
       finish_Q_columns(0, N_);
@@ -1843,283 +1738,6 @@ private:
       mw::store<NL>(inv, i, mw::mul(r, mw::sub(mw::from_u32<NL>(2), mw::mul(s, r))));
     });
   }
-  // the fixed-point image of a rows x cols operand: elements per group plane (kernels.hpp: fx_image_stride) and its
-  // allocation, zeroed once -- k_normalize_fx / k_fx_from_int only ever write the rows x cols elements, the pad stays zero
-  static size_t image_stride(size_t rows, size_t cols) { return std::max<size_t>(1, fx_image_stride<FX>(rows, cols, SYRK_RB)); }
-  void image_alloc(DevBuf<uint32_t> &fx, size_t stride)
-  {
-    fx.alloc(stride * fx_planes<FX>() + 4);
-    HIP_CHECK(hipMemsetAsync(fx.p, 0, fx.n * sizeof(uint32_t), stream_));
-  }
-  // k_syrk_fx3: the 21 products of a (tile, row split) in one workgroup (1), one Toom-4 group each (7), or one product each (21)
-  static int syrk_group_split()
-  {
-    if(!SYRK_TOOM4K)
-      return 1;
-    if(const char *e = std::getenv("SDPB_HIP_SYRK_GSPLIT"))
-      {
-        const int g = std::atoi(e);
-        return g == 1 ? 1 : (g == 7 || g == 9) ? SYRK_NPROD / 3 : SYRK_NPROD;
-      }
-    return SYRK_NPROD; // (21 or 27: one product per workgroup) measured (profiles/r04s_syrk3_variants.txt): C4 101.6 ms against 102.8 with 7, C3 1.23 against 1.55 ms
-  }
-  // The plan of one syrk_G call: the tile list is walked in chunks; every chunk is one product launch + its finishing
-  // kernels over tile-packed partial planes (kernels.hpp: syrk_packed_decode) that fit `budget_words` of `part`.
-  // Analogue of the reference's output windows (bigint_syrk_blas.cxx:200-220: Q is computed window by window when the
-  // residues of the whole output do not fit --maxSharedMemory, BigInt_Shared_Memory_Syrk_Context.cxx:149-215).
-  struct SyrkPlan
-  {
-    int ntile = 0, chunk_tiles = 0, nchunk = 0; // tiles of the call, tiles per chunk (a multiple of 8 unless one chunk), chunks
-    int nsplit_first = 1;                       // row splits of the first chunk (all chunks but a shorter last one)
-    size_t part_words = 0;                      // words of `part` the call needs
-    bool uses_part = false;
-  };
-  SyrkPlan last_syrk_plan_;                  // of the latest syrk_G call (sdpb_hip_memory_plan, the bench line)
-  size_t syrk_part_default_words_ = 0;       // budget found by build_layout()
-  size_t max_shared_bytes_ = 0;              // sdpb_hip_set_max_shared_memory (0: not set)
-  // row splits of a launch over `tiles` tiles: the occupancy rule of syrk_row_splits, bounded by the partial planes
-  // that fit `budget_words`, and no split without rows
-  int syrk_splits_for(int tiles, unsigned nrows, size_t budget_words) const
-  {
-    const int slots = num_cus_ * syrk_waves_per_simd<FX>();
-    int nsplit = syrk_row_splits(tiles * syrk_group_split(), nrows, slots, SYRK_RB, SYRK_SPLIT_ROWS);
-    const size_t per_split = (size_t)SYRK_PART_PLANES * tiles * SYRK_EDGE * SYRK_EDGE;
-    if(budget_words && (size_t)nsplit * per_split > budget_words)
-      nsplit = (int)std::max<size_t>(1, budget_words / per_split);
-    while(nsplit > 1 && (size_t)(nsplit - 1) * (cdiv(cdiv(nrows, nsplit), SYRK_RB) * SYRK_RB) >= nrows)
-      --nsplit; // (forced split counts on small inputs: the last split must own a row -- its planes are summed)
-    return nsplit;
-  }
-  SyrkPlan syrk_plan(int ntile, unsigned nrows, size_t budget_words) const
-  {
-    SyrkPlan pl;
-    pl.ntile = ntile;
-    const size_t tile_words = (size_t)SYRK_PART_PLANES * SYRK_EDGE * SYRK_EDGE; // one split of one tile
-    const int nsplit_all = syrk_splits_for(ntile, nrows, 0);
-    pl.uses_part = nsplit_all > 1 || SYRK_TOOM4;
-    pl.chunk_tiles = ntile;
-    pl.nchunk = ntile ? 1 : 0;
-    pl.nsplit_first = nsplit_all;
-    if(!pl.uses_part || !ntile)
-      return pl;
-    const size_t need = (size_t)nsplit_all * tile_words * ntile;
-    if(budget_words && need > budget_words)
-      {
-        // as few chunks as fit, of equal size: every launch stays far above the chip's resident workgroups
-        const size_t bw = std::max(budget_words, tile_words); // one tile, one split: the smallest chunk
-        int nchunk = (int)cdiv(need, bw);
-        for(;; ++nchunk)
-          {
-            int ct = (int)cdiv(ntile, nchunk);
-            if(ct >= 64)
-              ct = (int)(cdiv(ct, 8) * 8); // whole rounds of the eight XCDs
-            pl.chunk_tiles = std::min(ntile, ct);
-            pl.nsplit_first = syrk_splits_for(pl.chunk_tiles, nrows, bw);
-            if((size_t)pl.nsplit_first * tile_words * pl.chunk_tiles <= bw || pl.chunk_tiles <= 1)
-              break;
-          }
-        pl.nchunk = (int)cdiv(ntile, pl.chunk_tiles);
-      }
-    pl.part_words = (size_t)pl.nsplit_first * tile_words * pl.chunk_tiles;
-    return pl;
-  }
-  // words of partial planes a syrk_G call may use: SDPB_HIP_SYRK_PART_BYTES (tests, shared GPUs), else what the
-  // window budget -- sdpb_hip_set_max_shared_memory (--maxSharedMemory), else what build_layout() found free on the
-  // device -- leaves beside an image of `image_words`.  Never 0 ("unbounded") for a non-zero bound: at least one word,
-  // i.e. one-tile chunks (round-5 advisor).
-  size_t window_budget_words() const { return max_shared_bytes_ ? std::max<size_t>(1, max_shared_bytes_ / sizeof(uint32_t)) : syrk_part_default_words_; }
-  size_t syrk_part_budget_words(size_t image_words) const
-  {
-    if(const char *e = std::getenv("SDPB_HIP_SYRK_PART_BYTES"))
-      return std::max<size_t>(1, (size_t)std::max(1.0, std::atof(e)) / sizeof(uint32_t));
-    const size_t w = window_budget_words();
-    return std::max<size_t>(1, w - std::min(image_words, w / 2)); // (an image that could not be split -- chased Q' -- does not starve the planes)
-  }
-  size_t syrk_part_budget_words() const { return syrk_part_budget_words(fx_.n); }
-  // The INPUT window of the Q stage: the fixed-point image of P' is built for `chunk_rows` rows at a time (k_normalize_fx
-  // into ONE bounded buffer), each window's product is accumulated into Q' (k_acc_add_tri) -- the reference splits its
-  // input residue window by rows the same way when all rows do not fit --maxSharedMemory
-  // (BigInt_Shared_Memory_Syrk_Context.cxx:70-110,172-186: input_window_split_factor; bigint_syrk_blas.cxx:239-285 loops
-  // over the input windows).  Everything is exact integer arithmetic, so Q' keeps every bit whatever the split.
-  struct QWindow
-  {
-    unsigned chunk_rows = 0; // rows per input window (a multiple of the product's 2560-row splits where there are that many rows)
-    int chunks = 0;          // input windows per Q' (input_window_split_factor)
-    size_t stride = 0;       // elements per group plane of the window's image
-    size_t image_words = 0;  // words of the window's image buffer
-    size_t budget_words = 0; // what the image was allowed
-    bool bound_exceeded = false; // the budget is smaller than the smallest window (one pass of rows)
-  };
-  QWindow qwin_;
-  // words the image may take: SDPB_HIP_SYRK_IMAGE_BYTES (tests), else half of the window budget (the planes get the rest)
-  size_t image_budget_words() const
-  {
-    if(const char *e = std::getenv("SDPB_HIP_SYRK_IMAGE_BYTES"))
-      return std::max<size_t>(1, (size_t)std::max(1.0, std::atof(e)) / sizeof(uint32_t));
-    return std::max<size_t>(1, window_budget_words() / 2);
-  }
-  static size_t image_words_for(size_t rows, size_t cols) { return image_stride(rows, cols) * fx_planes<FX>() + 4; }
-  QWindow q_window(unsigned nrows, int N, bool one_chunk = false) const
-  {
-    QWindow w;
-    w.budget_words = image_budget_words();
-    const unsigned quantum = (unsigned)SYRK_RB;
-    unsigned rows = std::max(nrows, 1u);
-    if(!one_chunk && image_words_for(rows, (size_t)N) > w.budget_words)
-      {
-        // the most rows whose image fits, in whole passes of the product kernel
-        const size_t per_row = fx_row_slots<FX>((size_t)N) * fx_planes<FX>();
-        const size_t fixed = (size_t)64 * fx_planes<FX>() + 4;
-        size_t fit = w.budget_words > fixed ? (w.budget_words - fixed) / per_row : 0;
-        fit = fit / quantum * quantum;
-        if(fit < quantum)
-          {
-            fit = quantum;
-            w.bound_exceeded = true;
-          }
-        const unsigned f = (unsigned)cdiv(nrows, fit);
-        // equal windows; whole row splits of the product kernel where that still fits
-        unsigned cr = (unsigned)(cdiv(cdiv(nrows, f), quantum) * quantum);
-        if(SYRK_SPLIT_ROWS && cr > SYRK_SPLIT_ROWS)
-          {
-            const unsigned up = (unsigned)(cdiv(cr, SYRK_SPLIT_ROWS) * SYRK_SPLIT_ROWS);
-            if(up <= fit)
-              cr = up;
-          }
-        rows = cr;
-      }
-    if(one_chunk && image_words_for(rows, (size_t)N) > w.budget_words)
-      w.bound_exceeded = true;
-    w.chunk_rows = rows;
-    w.chunks = nrows ? (int)cdiv(nrows, rows) : 1;
-    w.stride = image_stride((size_t)rows, (size_t)N);
-    w.image_words = w.stride * fx_planes<FX>() + 4;
-    return w;
-  }
-  // Q' = sum over the input windows: `make(r0, rows)` writes the image of rows [r0, r0 + rows) into fx (stride w.stride);
-  // the first window's column sums and product go to acc, those of the others to acc2 and are added.  `mark`, if given,
-  // is called once, after the first window's column sums (the HIP events that bracket the dominant kernel).
-  template <class MakeImage, class Mark>
-  void syrk_G_windows(const QWindow &w, unsigned nrows, int N, DevBuf<uint32_t> &fx, uint32_t *acc, size_t acc_stride, DevBuf<uint32_t> &acc2,
-                      uint32_t *colsum_partial, const uint32_t *tiles_dev, DevBuf<uint32_t> &part, uint32_t *toomU, MakeImage &&make, Mark &&mark)
-  {
-    if(w.chunks > 1 && acc2.n < acc_stride * ACCW)
-      acc2.alloc(acc_stride * ACCW);
-    for(int c = 0; c < w.chunks; ++c)
-      {
-        const size_t r0 = (size_t)c * w.chunk_rows;
-        const unsigned rows = (unsigned)std::min<size_t>(w.chunk_rows, nrows - r0);
-        if(c > 0 && rows < w.chunk_rows) // a shorter last window: the rows behind it still hold the previous window
-          HIP_CHECK(hipMemsetAsync(fx.p, 0, fx.n * sizeof(uint32_t), stream_));
-        make(r0, rows);
-        uint32_t *out = c == 0 ? acc : acc2.p;
-        const unsigned slices = (unsigned)std::min<size_t>(128, std::max<size_t>(1, cdiv((size_t)rows, 64)));
-        syrk_column_sums(fx.p, w.stride, rows, N, out, acc_stride, colsum_partial, slices, toomU);
-        if(c == 0)
-          mark();
-        syrk_G(fx.p, w.stride, rows, N, out, acc_stride, tiles_dev, part, toomU, -1, 0, -1, w.image_words);
-        if(c > 0)
-          launch(k_acc_add_tri<ACCW>, dim3(cdiv(acc_stride, WG)), dim3(WG), stream_, acc, (const uint32_t *)acc2.p, acc_stride, N);
-      }
-    last_windows_ = w.chunks;
-  }
-  int last_windows_ = 1;
-  // G = sum_r a'_ri a'_rj into acc (kernels.hpp: k_syrk_fx), rows split over workgroups when
-  // that fills the last round of resident workgroups better; `part` grows on demand (never beyond the budget)
-  // ntile_sub >= 0: only the `ntile_sub` tiles tiles_dev points at, which cover the columns [col0, col1) of the lower
-  // triangle (a chunk of the chased Q'; the list comes from syrk_tile_order(N, split))
-  void syrk_G(const uint32_t *fx, size_t fx_stride, unsigned nrows, int N, uint32_t *acc, size_t acc_stride, const uint32_t *tiles_dev,
-              DevBuf<uint32_t> &part, const uint32_t *toomU = nullptr, int ntile_sub = -1, int col0 = 0, int col1 = -1, size_t image_words = 0)
-  {
-    if(SYRK_TOOM4 && !toomU)
-      throw SolverError(4, "syrk_G: the Toom-4 image needs the column terms of syrk_column_sums");
-    const unsigned tiles = cdiv(N, SYRK_EDGE);
-    const int ntile = ntile_sub >= 0 ? ntile_sub : (int)(tiles * (tiles + 1) / 2);
-    if(col1 < 0)
-      col1 = N;
-    if(ntile == 0 || col1 <= col0)
-      return;
-    const int gsplit = syrk_group_split();
-    // (the plan is made for the window's full height, so that a shorter last window reuses the same buffer)
-    const SyrkPlan pl = syrk_plan(ntile, nrows, syrk_part_budget_words(image_words ? image_words : fx_.n));
-    if(pl.uses_part && part.n < pl.part_words)
-      part.alloc(pl.part_words);
-    last_syrk_plan_ = pl;
-    constexpr size_t TW = (size_t)SYRK_EDGE * SYRK_EDGE;
-    for(int t0 = 0; t0 < ntile; t0 += pl.chunk_tiles)
-      {
-        const int nt = std::min(pl.chunk_tiles, ntile - t0);
-        const uint32_t *tl = tiles_dev + t0;
-        const int nsplit = nt == pl.chunk_tiles ? pl.nsplit_first : std::min(pl.nsplit_first, syrk_splits_for(nt, nrows, pl.part_words));
-        const unsigned rps = cdiv(cdiv(nrows, nsplit), SYRK_RB) * SYRK_RB;
-        const size_t ps = (size_t)nt * TW, total = ps; // plane stride of the chunk's partial planes = its packed words
-        const bool packed = pl.uses_part;
-        uint32_t *out = packed ? part.p : acc;
-        const size_t os = packed ? ps : acc_stride;
-        if constexpr(SYRK_TOOM4)
-          {
-            if constexpr(SYRK_TOOM4K)
-              launch(k_syrk_fx3<FX, SYRK_RB>, dim3(8 * cdiv((size_t)nt * nsplit * gsplit, 8)), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl,
-                     nt, nsplit, rps, gsplit);
-            else
-              launch(k_syrk_fx2<FX, SYRK_RB, true>, dim3(8 * cdiv((size_t)nt * nsplit, 8)), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl, nt,
-                     nsplit, rps, (const uint32_t *)zero_piece_.p, 1);
-            int nsum = nsplit;
-            if constexpr(SYRK_TOOM4K)
-              if(nsplit > 1)
-                {
-                  launch(k_syrk3_sum_splits<FX>, dim3(cdiv(total, WG), SYRK_NPROD), dim3(WG), stream_, part.p, nsplit, ps, tl, total, N, col0, col1);
-                  nsum = 1;
-                }
-            if constexpr(SYRK_TOOM5K)
-              launch(k_syrk5_finish<FX>, dim3(cdiv(total, WG)), dim3(WG), stream_, (const uint32_t *)part.p, nsum, ps, tl, total,
-                     (const uint32_t *)toomU, acc, acc_stride, N, col0, col1);
-            else
-              launch(k_syrk4_finish<FX>, dim3(cdiv(total, WG)), dim3(WG), stream_, (const uint32_t *)part.p, nsum, ps, tl, total,
-                     (const uint32_t *)toomU, acc, acc_stride, N, col0, col1);
-            continue;
-          }
-        else if constexpr(SYRK_TWO_LEVEL)
-          launch(k_syrk_fx2<FX, SYRK_RB>, dim3(8 * cdiv((size_t)nt * nsplit, 8)), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl, nt, nsplit,
-                 rps, (const uint32_t *)zero_piece_.p, (int)packed);
-        else
-          launch(k_syrk_fx<FX, SYRK_RB>, dim3(8 * cdiv((size_t)nt * nsplit, 8)), dim3(WG), stream_, fx, fx_stride, nrows, N, out, os, tl, nt, nsplit,
-                 rps, (int)packed);
-        if(packed)
-          launch(k_syrk_reduce<FX>, dim3(cdiv(total, WG)), dim3(WG), stream_, (const uint32_t *)part.p, nsplit, ps, tl, total, acc, acc_stride, N,
-                 col0, col1);
-      }
-  }
-  // S_n = sum_r a'_rn behind the N x N block of acc (kernels.hpp: k_fx_colsum)
-  void syrk_column_sums(const uint32_t *fx, size_t fx_stride, unsigned nrows, int N, uint32_t *acc, size_t acc_stride, uint32_t *partial,
-                        unsigned slices, uint32_t *toomU = nullptr)
-  {
-    const unsigned rows_per_slice = cdiv(nrows, slices);
-    if constexpr(SYRK_TOOM4)
-      {
-        if(!toomU)
-          throw SolverError(4, "syrk_column_sums: the Toom-4 image needs a buffer for its column terms");
-        if constexpr(SYRK_TOOM5K)
-          {
-            launch(k_fx_colsum5<FX>, dim3(cdiv(N, 64), slices), dim3(WG), stream_, fx, fx_stride, nrows, N, rows_per_slice, partial);
-            launch(k_fx_colsum5_final<FX>, dim3(cdiv(N, WG)), dim3(WG), stream_, (const uint32_t *)partial, (int)slices, N, acc, acc_stride, toomU,
-                   (unsigned long long)nrows);
-            return;
-          }
-        launch(k_fx_colsum2<FX, true>, dim3(cdiv(N, 64), slices), dim3(WG), stream_, fx, fx_stride, nrows, N, rows_per_slice, partial);
-        launch(k_fx_colsum4_final<FX>, dim3(cdiv(N, WG)), dim3(WG), stream_, (const uint32_t *)partial, (int)slices, N, acc, acc_stride, toomU,
-               (unsigned long long)nrows);
-        return;
-      }
-    else if constexpr(SYRK_TWO_LEVEL)
-      {
-        launch(k_fx_colsum2<FX>, dim3(cdiv(N, 64), slices), dim3(WG), stream_, fx, fx_stride, nrows, N, rows_per_slice, partial);
-        launch(k_fx_colsum2_final<FX>, dim3(cdiv(N, WG)), dim3(WG), stream_, (const uint32_t *)partial, (int)slices, N, acc, acc_stride);
-        return;
-      }
-    launch(k_fx_colsum<FX>, dim3(cdiv(N, 64), slices), dim3(WG), stream_, fx, fx_stride, nrows, N, rows_per_slice, partial);
-    launch(k_fx_colsum_final<FX>, dim3(cdiv(N, WG)), dim3(WG), stream_, (const uint32_t *)partial, (int)slices, N, acc, acc_stride);
-  }
   // exact cross-GPU sum of the fixed-point Q' images
   void reduce_Q_accumulators(int c0 = 0, int c1 = -1, bool with_sums = true)
   {
@@ -2128,12 +1746,12 @@ private:
       c1 = N_;
     const size_t T = tri_packed_offset(N_, c1) - tri_packed_offset(N_, c0) + (with_sums ? (size_t)N_ : 0);
     const dim3 grid(cdiv(N_, WG), c1 - c0 + (with_sums ? 1 : 0));
-    launch(k_widen_tri_u64<0>, grid, dim3(WG), stream_, (const uint32_t *)acc_.p, acc_stride_, N_, (int)ACCW, acc64_.p, c0, c1, (int)with_sums);
+    launch(k_widen_tri_u64<0>, grid, dim3(WG), stream_, (const uint32_t *)syrk_.acc.p, syrk_.acc_stride, N_, (int)Syrk::ACCW, acc64_.p, c0, c1, (int)with_sums);
     xc_allreduce_calls_ += 1;
-    xc_allreduce_bytes_ += (double)(T * ACCW * 8);
-    note_collective(COLL_ALLREDUCE, T * ACCW * 8, -1);
-    comm().allreduce_sum_u64(acc64_.p, T * ACCW, stream_);
-    launch(k_narrow_tri_carry<0>, grid, dim3(WG), stream_, (const unsigned long long *)acc64_.p, N_, (int)ACCW, acc_.p, acc_stride_, c0, c1,
+    xc_allreduce_bytes_ += (double)(T * Syrk::ACCW * 8);
+    note_collective(COLL_ALLREDUCE, T * Syrk::ACCW * 8, -1);
+    comm().allreduce_sum_u64(acc64_.p, T * Syrk::ACCW, stream_);
+    launch(k_narrow_tri_carry<0>, grid, dim3(WG), stream_, (const unsigned long long *)acc64_.p, N_, (int)Syrk::ACCW, syrk_.acc.p, syrk_.acc_stride, c0, c1,
            (int)with_sums);
   }
   // in-place broadcast on the main stream through whatever the exchange runs on
@@ -2954,33 +2572,25 @@ public:
     if(op != "syrk" || a <= 0 || b <= 0)
       throw SolverError(4, "bench_op: unknown op " + op);
     const int rows = a, cols = b;
-    const size_t cnt = (size_t)rows * cols;
-    DevBuf<uint32_t> fx, acc, part, tl;
-    const size_t fxs = image_stride((size_t)rows, (size_t)cols);
-    image_alloc(fx, fxs);
+    Syrk ws(&syrk_); // the whole image in one window; column terms of the Toom-4 image zero: the timing does not depend on them
+    ws.prepare((size_t)rows, cols, stream_, /*one_chunk=*/true);
     {
       // pseudo-random limbs with the top bit of every word clear (valid pieces of every image layout)
-      uint32_t *p = fx.p;
-      foreach(fxs * fx_planes<FX>(), [=] __device__(size_t i) {
+      uint32_t *p = ws.image.p;
+      foreach(ws.win.stride * fx_planes<FX>(), [=] __device__(size_t i) {
         uint64_t z = (uint64_t)i * 0x9E3779B97F4A7C15ull + 0x1234567ull;
         z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
         z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        p[i] = (uint32_t)(z >> (SYRK_TOOM5K ? 37 : 33)); // (limbs of the lazy-carry image are < 2^28)
+        p[i] = (uint32_t)(z >> (Syrk::SYRK_TOOM5K ? 37 : 33)); // (limbs of the lazy-carry image are < 2^28)
       });
     }
-    const size_t as = (size_t)cols * cols + cols;
-    acc.alloc(as * ACCW);
-    tl.upload(syrk_tile_order(cols, 0, nullptr, SYRK_EDGE));
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
     HIP_CHECK(hipEventCreate(&e1));
-    DevBuf<uint32_t> tu; // column terms of the Toom-4 image (zeros: the timing does not depend on them)
-    tu.alloc(TOOMU_WORDS * cols);
-    HIP_CHECK(hipMemsetAsync(tu.p, 0, tu.n * sizeof(uint32_t), stream_));
-    syrk_G(fx.p, fxs, (unsigned)rows, cols, acc.p, as, (const uint32_t *)tl.p, part, tu.p, -1, 0, -1, fx.n); // warm-up (sizes `part`)
+    ws.G(stream_, ws.all()); // warm-up
     HIP_CHECK(hipEventRecord(e0, stream_));
     for(int r = 0; r < std::max(reps, 1); ++r)
-      syrk_G(fx.p, fxs, (unsigned)rows, cols, acc.p, as, (const uint32_t *)tl.p, part, tu.p, -1, 0, -1, fx.n);
+      ws.G(stream_, ws.all());
     HIP_CHECK(hipEventRecord(e1, stream_));
     HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0;
@@ -3024,24 +2634,19 @@ public:
            (const BlockDesc *)dbd.p, cols);
     launch(k_sum_partials<NL>, dim3(cdiv(cols, SP_ROWS)), dim3(WG), stream_, part.cptr(), 1, cols, nrm.cptr(), 0, 1, nrm.ptr());
     norms_to_inverse(nrm.ptr(), inv.ptr(), (size_t)cols);
-    DevBuf<uint32_t> fx, acc, acc2, partial, tl, spart;
     DevBuf<int> qf;
-    const QWindow win = q_window((unsigned)rows, cols); // the same input windows as the iteration (SDPB_HIP_SYRK_IMAGE_BYTES, --maxSharedMemory)
-    image_alloc(fx, win.stride);
-    const size_t as = (size_t)cols * cols + cols;
-    acc.alloc(as * ACCW);
-    const unsigned slices = (unsigned)std::min<size_t>(128, std::max<size_t>(1, cdiv((size_t)rows, 64)));
-    partial.alloc((size_t)slices * COLSUM_WORDS * cols);
-    DevBuf<uint32_t> tu;
-    tu.alloc(TOOMU_WORDS * cols);
-    tl.upload(syrk_tile_order(cols, 0, nullptr, SYRK_EDGE));
-    syrk_G_windows(win, (unsigned)rows, cols, fx, acc.p, as, acc2, partial.p, (const uint32_t *)tl.p, spart, tu.p,
-                   [&](size_t r0, unsigned nr) {
-                     const size_t n = (size_t)nr * cols;
-                     launch(k_normalize_fx<NL, FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, mw::offset(PT.cptr(), r0 * (size_t)cols), n, cols, inv.cptr(), fx.p,
-                            win.stride);
-                   },
-                   [] {});
+    Syrk ws(&syrk_); // the same input windows as the iteration (SDPB_HIP_SYRK_IMAGE_BYTES, --maxSharedMemory)
+    ws.prepare((size_t)rows, cols, stream_);
+    const size_t as = ws.acc_stride;
+    DevBuf<uint32_t> &acc = ws.acc;
+    ws.G_windows(
+      stream_,
+      [&](size_t r0, unsigned nr) {
+        const size_t n = (size_t)nr * cols;
+        launch(k_normalize_fx<NL, FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, mw::offset(PT.cptr(), r0 * (size_t)cols), n, cols, inv.cptr(), ws.image.p,
+               ws.win.stride);
+      },
+      [] {});
     qf.alloc(4);
     HIP_CHECK(hipMemsetAsync(qf.p, 0, 4 * sizeof(int), stream_));
     launch(k_syrk_unbias<FX>, dim3(cdiv((size_t)cols * cols, WG)), dim3(WG), stream_, acc.p, as, cols, (unsigned long long)rows, (size_t)0,
@@ -3129,26 +2734,20 @@ public:
             h[(k + 1) * cnt + idx] = n.w[k];
           h[idx] = (negative && !n.w.empty()) ? 1u : 0u;
         }
-    DevBuf<uint32_t> staged, fx, acc, acc2, partial;
+    DevBuf<uint32_t> staged;
     staged.upload(h);
-    const QWindow win = q_window((unsigned)rows, cols); // the same input windows as the iteration (SDPB_HIP_SYRK_IMAGE_BYTES, --maxSharedMemory)
-    image_alloc(fx, win.stride);
-    const size_t as = (size_t)cols * cols + cols;
-    acc.alloc(as * ACCW);
-    const unsigned slices = (unsigned)std::min<size_t>(128, std::max<size_t>(1, cdiv((size_t)rows, 64)));
-    partial.alloc((size_t)slices * COLSUM_WORDS * cols);
-    DevBuf<uint32_t> tu;
-    tu.alloc(TOOMU_WORDS * cols);
-    DevBuf<uint32_t> tl;
-    tl.upload(syrk_tile_order(cols, 0, nullptr, SYRK_EDGE));
-    DevBuf<uint32_t> part;
-    syrk_G_windows(win, (unsigned)rows, cols, fx, acc.p, as, acc2, partial.p, (const uint32_t *)tl.p, part, tu.p,
-                   [&](size_t r0, unsigned nr) {
-                     const size_t n = (size_t)nr * cols;
-                     launch(k_fx_from_int<FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, (const uint32_t *)staged.p + r0 * (size_t)cols, cnt, n, cols,
-                            fx.p, win.stride);
-                   },
-                   [] {});
+    Syrk ws(&syrk_); // the same input windows as the iteration (SDPB_HIP_SYRK_IMAGE_BYTES, --maxSharedMemory)
+    ws.prepare((size_t)rows, cols, stream_);
+    const size_t as = ws.acc_stride;
+    DevBuf<uint32_t> &acc = ws.acc;
+    ws.G_windows(
+      stream_,
+      [&](size_t r0, unsigned nr) {
+        const size_t n = (size_t)nr * cols;
+        launch(k_fx_from_int<FX>, dim3(cdiv(n, WG)), dim3(WG), stream_, (const uint32_t *)staged.p + r0 * (size_t)cols, cnt, n, cols, ws.image.p,
+               ws.win.stride);
+      },
+      [] {});
     launch(k_syrk_unbias<FX>, dim3(cdiv((size_t)cols * cols, WG)), dim3(WG), stream_, acc.p, as, cols, (unsigned long long)rows, (size_t)0,
            (size_t)cols * cols);
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -3164,10 +2763,10 @@ public:
               continue;
             }
           mw::BigNat n;
-          n.w.resize(ACCW);
-          for(int k = 0; k < ACCW; ++k)
+          n.w.resize(Syrk::ACCW);
+          for(int k = 0; k < Syrk::ACCW; ++k)
             n.w[k] = a[(size_t)k * as + idx];
-          const bool negative = n.w[ACCW - 1] >> 31;
+          const bool negative = n.w[Syrk::ACCW - 1] >> 31;
           if(negative)
             {
               uint64_t carry = 1;

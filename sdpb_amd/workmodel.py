@@ -86,7 +86,7 @@ def _fx(nl: int):
 
 
 def syrk_row_splits(ntile: int, nrows: int, slots: int, rb: int, max_rows: int) -> int:
-    """kernels.hpp: syrk_row_splits"""
+    """syrk_stage.hpp: syrk_row_splits"""
     import math
     smin = 1
     while max_rows and smin < 32 and nrows // smin > max_rows and nrows // (smin + 1) >= 64 * rb:
@@ -103,7 +103,7 @@ def syrk_row_splits(ntile: int, nrows: int, slots: int, rb: int, max_rows: int) 
 
 
 def q_window(rows: int, N: int, nl: int, image_budget_bytes: int):
-    """solver.hpp: Solver::q_window -- (rows per input window, windows, bytes of the window's image)."""
+    """syrk_stage.hpp: FxSyrk::q_window -- (rows per input window, windows, bytes of the window's image)."""
     fx, words, edge, planes, rb, waves, toom4, toom4k = _fx(nl)
 
     slots = -(-N // 32) * 32 if fx == 16 else N   # kernels.hpp: fx_row_slots (tile column order of the lazy-carry image)
@@ -166,7 +166,7 @@ def planned_footprint(dims, num_points, N, precision, owners=None, rank=0, world
             q_bytes += ((N * pb + pb * pb + pb) * (nl + 1) + 2) * 4
     out["Q"] = q_bytes
     out["vectors_and_small"] = (5 * max(rows, 1) + 6 * max(vecn, 1) + 8 * N + 2 * max(jl, 1) * N) * W
-    # the two windows of the Q stage, planned together against what the rest leaves (solver.hpp: build_layout, q_window, syrk_plan)
+    # the two windows of the Q stage, planned together against what the rest leaves (syrk_stage.hpp: FxSyrk::prepare, q_window, syrk_plan)
     rest = sum(out.values())
     free = (hbm_bytes if free_bytes is None else free_bytes) - rest
     reserve = hbm_bytes // 16 + (1 << 30)

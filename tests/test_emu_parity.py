@@ -29,7 +29,7 @@ def test_emulated_library_matches_reference_golden(name, limit):
 _INT_SYRK = [(128, 37, 21, None), (128, 70, 21, "3"), (512, 45, 18, None), (512, 100, 18, "3"), (512, 40, 47, None), (512, 70, 81, "2"),
              (512, 33, 34, None), (768, 33, 17, None), (768, 37, 45, "2"), (664, 20, 17, None), (1024, 40, 18, None), (1024, 40, 18, "2"),
              (1024, 35, 49, None), (1280, 36, 17, None), (1280, 70, 17, "2")]
-# a memory budget (bytes) below the partial planes of the whole output: Q' in chunks of output tiles (Solver::syrk_plan; 32 x 32
+# a memory budget (bytes) below the partial planes of the whole output: Q' in chunks of output tiles (FxSyrk::syrk_plan; 32 x 32
 # tiles at 512 ... 1024 bits, 16 x 16 else) -- the analogue of the reference's output windows (bigint_syrk_blas.cxx:200-220)
 _INT_SYRK_CHUNKED = [(512, 70, 81, "2", 1.0e6), (512, 100, 97, None, 6.0e5), (128, 70, 41, "3", 2.5e4), (1024, 40, 49, "2", 1.6e6),
                      (1280, 70, 33, "2", 7.0e5), (768, 37, 45, "2", 1.3e6)]
@@ -81,7 +81,7 @@ def test_emulated_int_syrk_is_exact(precision, rows, cols, splits, budget, monke
 
 
 # an image budget (bytes) below the fixed-point image of all rows: P' in row chunks through ONE bounded image buffer, each
-# window's product accumulated into Q' (Solver::q_window / syrk_G_windows) -- the analogue of the reference's input windows
+# window's product accumulated into Q' (FxSyrk::q_window / G_windows) -- the analogue of the reference's input windows
 # (BigInt_Shared_Memory_Syrk_Context.cxx:70-110,172-186: input_window_split_factor; bigint_syrk_blas.cxx:239-285);
 # (precision, rows, cols, forced row splits, image budget, partial-plane budget or None)
 _INT_SYRK_WINDOWS = [(512, 100, 18, None, 1.1e5, None), (512, 140, 47, "2", 6.0e5, 1.0e6), (128, 70, 21, "3", 2.5e4, None),

@@ -174,7 +174,7 @@ def test_int_syrk_bit_exact(precision, rows, cols, splits, monkeypatch):
 def test_int_syrk_in_chunks_under_a_memory_budget_is_bit_exact(precision, rows, cols, splits, budget, monkeypatch):
     """The analogue of the reference's output windows (bigint_syrk_blas.cxx:200-220, BigInt_Shared_Memory_Syrk_Context.cxx:149-215,
     --maxSharedMemory): a budget far below the partial planes of the whole Q' (row splits x limb planes x tile-packed lower
-    triangle) makes Solver::syrk_G walk the output tiles in chunks through ONE bounded buffer; every entry stays bit-exact
+    triangle) makes FxSyrk::G walk the output tiles in chunks through ONE bounded buffer; every entry stays bit-exact
     against GMP."""
     from oracle.oracle import Oracle
     if splits:
@@ -205,7 +205,7 @@ def test_int_syrk_in_chunks_under_a_memory_budget_is_bit_exact(precision, rows, 
 def test_int_syrk_with_the_image_in_row_windows_is_bit_exact(precision, rows, cols, splits, image_budget, part_budget, monkeypatch):
     """The analogue of the reference's INPUT windows (BigInt_Shared_Memory_Syrk_Context.cxx:70-110,172-186:
     input_window_split_factor; bigint_syrk_blas.cxx:239-285 loops over them): an image budget far below the fixed-point image of
-    all rows makes Solver::syrk_G_windows build the image for one row window at a time in ONE bounded buffer and add each
+    all rows makes FxSyrk::G_windows build the image for one row window at a time in ONE bounded buffer and add each
     window's product into Q' (k_acc_add_tri) -- every entry stays bit-exact against GMP, alone and together with chunked
     output windows; so does the whole syrk_Q stage (norms, normalise-and-shift per window, diagonal check, restore)."""
     from oracle.oracle import Oracle

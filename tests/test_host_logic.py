@@ -331,3 +331,20 @@ def test_tile_dot_products_are_exact_against_gmp(tmp_path):
     assert r.returncode == 0, r.stderr
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.count(" 0 failures") == 8, r.stdout + r.stderr
+
+
+def test_syrk_planners_keep_what_the_launches_rely_on(tmp_path):
+    """sdpb_amd/csrc/syrk_stage.hpp (FxSyrk<FX>: syrk_plan, syrk_splits_for, q_window) on the host, without a device and under
+    AddressSanitizer + UBSan (tests/shim/syrk_plan_check.cpp): for the image width of each of the ten compiled limb counts,
+    over N = 1 ... 2048, 1 ... 700 000 rows, forced row splits and budgets from nothing to 10^10 bytes, the chunks of the tile
+    list cover it and none is empty, the last row split of every chunk (a shorter last one included) owns a row and its planes
+    fit the buffer, the planes stay inside a non-zero budget or are one tile in one split, the input windows cover the rows in
+    whole passes of the product kernel, and the image stays inside its budget unless the plan says the bound is exceeded."""
+    import subprocess
+    exe = tmp_path / "syrk_plan_check"
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-I" + os.path.join(libs.ROOT, "tests", "emu", "include"),
+                        "-I" + os.path.join(libs.ROOT, "sdpb_amd", "csrc"), "-DSDPB_NO_RCCL", "-Wno-unknown-pragmas", "-Wno-attributes",
+                        os.path.join(libs.ROOT, "tests", "shim", "syrk_plan_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.count(" 0 failures") == 10 and not r.stderr, r.stdout + r.stderr
