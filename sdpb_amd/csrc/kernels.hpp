@@ -2064,10 +2064,13 @@ template <int FX> constexpr bool fx_toom4k()
 // points 0, 1, -1, 2, -2, 1/2, -1/2, 3, inf (every value < 121 b < 2^109; the three signed points stored with a bias
 // K = 2 b, 10 b, 10 b that the column sums remove exactly, as in Toom-4), each evaluated value split once more
 // (Karatsuba: halves of H = 55 bits and their sum, < 2^56 = two 28-bit limbs): 27 products of 2 x 2 limbs per row pair =
-// 108 multiply-adds of ONE instruction each, against the 84 pairs = 168 instructions of Toom-4 x Karatsuba -- and
+// 108 multiply-adds of ONE instruction each (81 since the second level, below), against the 84 pairs = 168 instructions of Toom-4 x Karatsuba -- and
 // FB = 5 w - 1 = 509 fraction bits, where Toom-4 x Karatsuba keeps 487 and the reference 512.  The interpolation (a 9 x 9
 // integer matrix with exact divisions, derived in profiles/tools/toom5_matrix.py) runs once per output element in
-// k_syrk5_finish.  Image: 27 pieces of two words (limbs < 2^28), group 3 g + u, g the point, u in (lo, hi, mid).
+// k_syrk5_finish.  A SECOND Karatsuba level on the 2 x 2-limb products makes them three one-limb products: 81 multiply-adds
+// per row pair (k_syrk5_k2).  Its adds cannot go into the row loop (a v_add costs the issue slot of a multiply-add), so the
+// image carries the sums.  Image: 27 pieces (x0, x1) of limbs < 2^28, group 3 g + u, g the point, u in (lo, hi, mid), as three
+// one-word planes 9 g + 3 u + t, t in (x0, x1, xm = x0 + x1 <= 2^29 - 2): 81 words per element.
 template <int FX> constexpr bool fx_toom5k()
 {
 #if defined(SDPB_SYRK_NO_TOOM5K)
@@ -2086,17 +2089,17 @@ template <int FX> constexpr int fx_part_limbs() { return fx_toom5k<FX>() ? 5 : 2
 template <int FX> constexpr int toom_wb() { return fx_toom5k<FX>() ? 102 : 32 * (FX / 4) - (fx_toom4k<FX>() ? 6 : 4); }
 template <int FX> constexpr int fx_planes()
 {
-  return fx_toom5k<FX>() ? 27 * 2 : fx_toom4k<FX>() ? 21 * (FX / 8) : fx_toom4<FX>() ? 7 * (FX / 4) : fx_two_level<FX>() ? 9 * (FX / 4) : 3 * (FX / 2);
+  return fx_toom5k<FX>() ? 27 * 3 : fx_toom4k<FX>() ? 21 * (FX / 8) : fx_toom4<FX>() ? 7 * (FX / 4) : fx_two_level<FX>() ? 9 * (FX / 4) : 3 * (FX / 2);
 }
 template <int FX> constexpr int fx_frac_bits()
 {
   return fx_toom5k<FX>() ? 5 * toom_wb<FX>() - 1 : fx_toom4<FX>() ? 4 * toom_wb<FX>() - 1 : fx_two_level<FX>() ? 32 * FX - 7 : 32 * FX - 3;
 }
-// TILE COLUMN ORDER of the lazy-carry image (fx_toom5k): inside every group of 32 columns -- a tile of k_syrk_fx3 -- column c
-// sits in slot 2 (c % 16) + (c % 32) / 16, so that the two pieces a lane of that kernel multiplies (columns l and l + 16 of
-// the tile) are 16 contiguous bytes of the staged row: one ds_read_b128 per operand and row.  Every other image keeps its
-// columns in their natural order (the identity).
-template <int FX> constexpr int fx_col_slot(int c) { return fx_toom5k<FX>() ? 32 * (c / 32) + 2 * (c % 16) + (c % 32) / 16 : c; }
+// TILE COLUMN ORDER of the lazy-carry image (fx_toom5k): inside every group of 32 columns -- a tile of k_syrk5_k2 -- column c
+// sits in slot 4 (c % 8) + (c % 32) / 8, so that the four one-word pieces a lane of that kernel multiplies (columns l,
+// l + 8, l + 16, l + 24 of the tile) are 16 contiguous bytes of the staged 128-byte row: one ds_read_b128 per operand and
+// row.  Every other image keeps its columns in their natural order (the identity).
+template <int FX> constexpr int fx_col_slot(int c) { return fx_toom5k<FX>() ? 32 * (c / 32) + 4 * (c % 8) + (c % 32) / 8 : c; }
 // slots per image row: with the tile column order the last group of a row has holes between its real columns (fewer than
 // 32 of them still reach up to slot 31), so the row is padded to whole groups of 32 slots
 template <int FX> constexpr size_t fx_row_slots(size_t cols) { return fx_toom5k<FX>() ? (cols + 31) / 32 * 32 : cols; }
@@ -2118,7 +2121,7 @@ template <int FX> constexpr size_t fx_image_stride(size_t rows, size_t cols, int
 {
   return fx_toom4k<FX>() ? (rows + rb - 1) / rb * rb * fx_row_slots<FX>(cols) + 64 : rows * cols;
 }
-// edge of the output tiles of the syrk kernel in use: k_syrk_fx3 gives a lane 2 x 2 outputs
+// edge of the output tiles of the syrk kernel in use: 32 x 32 for k_syrk_fx3 (2 x 2 outputs per lane of 256) and k_syrk5_k2 (4 x 4 per lane of 64)
 template <int FX> constexpr int syrk_tile_edge() { return fx_toom4k<FX>() ? 32 : 16; }
 
 // out = (x >> BIT0) mod 2^NB as OUT limbs (compile-time positions)
@@ -2390,6 +2393,7 @@ template <int FX> MW_HD void fx_store5(const uint32_t (&mag)[FX], bool negative,
   constexpr int TOPBIT = WB - 32 * (ML - 1); // bit of b = 2^WB inside the top limb of an evaluated piece
   static_assert(FB == 5 * WB - 1 && FB / 32 == FX - 1, "a' = v + 2^FB fills five pieces of WB bits");
   static_assert(TOPBIT >= 0 && TOPBIT + 7 <= 32 && WB + 7 <= 2 * H && H + 1 <= 2 * LB, "121 b fits, the halves fit two limbs");
+  static_assert(H - LB + 1 <= LB, "the upper limb of a half has H - LB bits, that of mid one more: every limb < 2^LB, their sum xm <= 2^(LB+1) - 2");
   uint32_t a[FX];
   uint64_t borrow = 0;
 #pragma unroll
@@ -2458,9 +2462,15 @@ template <int FX> MW_HD void fx_store5(const uint32_t (&mag)[FX], bool negative,
       const uint32_t s0 = lo[0] + hi[0];
       mid[0] = s0 & T5_MASK;
       mid[1] = lo[1] + hi[1] + (s0 >> LB);
-      piece_store<2>(fx + ((size_t)(3 * g + 0) * fx_stride + idx) * 2, lo);
-      piece_store<2>(fx + ((size_t)(3 * g + 1) * fx_stride + idx) * 2, hi);
-      piece_store<2>(fx + ((size_t)(3 * g + 2) * fx_stride + idx) * 2, mid);
+      // plane 9 g + 3 u + t: the limbs x0, x1 of piece u and their sum xm = x0 + x1 (second Karatsuba level: < 2^29)
+      const uint32_t *piece[3] = {lo, hi, mid};
+#pragma unroll
+      for(int u = 0; u < 3; ++u)
+        {
+          fx[(size_t)(9 * g + 3 * u + 0) * fx_stride + idx] = piece[u][0];
+          fx[(size_t)(9 * g + 3 * u + 1) * fx_stride + idx] = piece[u][1];
+          fx[(size_t)(9 * g + 3 * u + 2) * fx_stride + idx] = piece[u][0] + piece[u][1];
+        }
     }
 }
 
@@ -3748,18 +3758,12 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK_WAVES)
 // reads as the 4 x 4-limb product of k_syrk_fx2, and the same staging: 16-byte global_load_lds units of a row of
 // adjacent columns' pieces, [row][column][M3 limbs] in LDS.  Quadrants of the tile that hold no output (above the
 // diagonal of a diagonal tile, past column N) are skipped workgroup-wide, so the executed products are those of the
-// 16 x 16 tiling.  In lazy-carry mode (fx_toom5k) the image is in TILE COLUMN ORDER (fx_col_slot: columns l and l + 16 of a
-// tile in slots 2 l and 2 l + 1, image rows padded to whole groups of 32 slots), so the staged row -- still a verbatim copy
-// of 256 bytes of the image row -- holds a lane's two pieces of an operand as 16 contiguous bytes: ONE ds_read_b128 per
-// operand and row (4 LDS-array cycles, conflict-free, at full rate from one wavefront per SIMD) where the natural order
-// needs a ds_read2_b64 (8 cycles); the products and the output planes are the same.  One SWEEP over the split's rows = one of the 21 products: a pass per block of RBG rows, the column
+// 16 x 16 tiling.  (The lazy-carry image of fx_toom5k has a kernel of its own: k_syrk5_k2.)
+// One SWEEP over the split's rows = one of the 21 products: a pass per block of RBG rows, the column
 // accumulators (96 bits each, 4 x (2 M3 - 1) per lane) live in registers for the whole sweep and are folded when it ends.
 // The LDS reads of row r + 1 are issued before the products of row r (101.9 ms against 103.8 without: profiles/r04s_syrk3_variants.txt).
 #ifndef SDPB_SYRK3_WAVES
 #define SDPB_SYRK3_WAVES 3
-#endif
-#ifndef SDPB_SYRK3_LAZY_TRIP
-#define SDPB_SYRK3_LAZY_TRIP 32 // rows per trip of the lazy-carry row loop: the whole pass, every row's LDS offset an immediate
 #endif
 template <int FX, int RBG>
 __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
@@ -3768,11 +3772,8 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
 {
   // gsplit = 7 (21): a workgroup takes the three products of ONE Toom-4 group (one product) of its (tile, row split)
   // instead of all 21 (the sweeps are independent): more workgroups where the output has few tiles, a shorter tail everywhere
-  // LAZY (fx_toom5k: 27 products of pieces with 28-bit limbs): the column accumulators are plain 64-bit sums -- a multiply-add
-  // per limb pair and no carry instruction; they are carried into each other every second pass (64 rows)
-  constexpr bool LAZY = fx_toom5k<FX>();
   constexpr int M3 = FX / 8, A3 = fx_part_limbs<FX>(), NPROD = fx_nprod<FX>();
-  static_assert(M3 >= 2 && M3 <= 4 && (!LAZY || (M3 == 2 && RBG <= 32)), "accumulators of 2 x 2 outputs in registers; 2 x 32 rows between carries");
+  static_assert(M3 >= 2 && M3 <= 4 && !fx_toom5k<FX>(), "accumulators of 2 x 2 outputs in registers");
   // a staged row = the M3-limb pieces of the tile's 32 columns = ROWW words = UPR 16-byte units (a unit is two pieces at
   // M3 = 2, one at 4, and straddles pieces at 3: the row is contiguous in the image and in LDS either way)
   constexpr int ROWW = 32 * M3, UPR = ROWW / 4, NPAIR = RBG * UPR, GL = NPAIR / WG; // units per operand per pass, per lane
@@ -3802,7 +3803,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   __shared__ __attribute__((aligned(16))) uint32_t sb[2 * NPAIR * 4 + 64];
   uint64_t cc[4][2 * M3 - 1];
   uint32_t hh[4][2 * M3 - 1];
-  uint64_t dd[4][2 * M3 - 1]; // LAZY: the high words taken out of the columns (weight 2^32 of their column)
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr bool DIRECT = true; // (the host path of the emulation build stages through registers)
 #else
@@ -3811,8 +3811,7 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   // Staging of the NEXT pass: the image is padded with zero rows to a multiple of RBG and every row block a workgroup
   // touches lies inside it (fx3_image_stride), so a pass is the same per-lane offsets from a workgroup-uniform base:
   // no per-lane pointer selects.  Columns past N load whatever follows the row (the pad behind the last one): they
-  // only reach outputs that are not stored.  (LAZY: an image row is NS = fx_row_slots(N) slots, whole tiles, and the slots
-  // of the columns past N are zero pad.)
+  // only reach outputs that are not stored.
   const size_t NS = fx_row_slots<FX>((size_t)N);
   uint32_t va[DIRECT ? 1 : GL][4], vb[DIRECT ? 1 : GL][4];
   uint32_t offa[GL], offb[GL];
@@ -3879,19 +3878,13 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     // pass (vmcnt(0)) before the first read of this one -- those land in the other buffer; the barrier that ends the
     // pass waits for them
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    // LAZY (tile column order, fx_col_slot): the pieces of columns l and l + 16 of the tile are the 16 bytes at 16 l of the
-    // staged row -- one ds_read_b128 per operand and row, .x/.y the piece of column l, .z/.w that of column l + 16.  The 16
-    // lanes of a read's lane group that differ in li cover 256 contiguous bytes (every bank once); those that differ in lj
-    // read at most two 16-byte units (a broadcast each).  Else: the two pieces are 16 columns = 128 bytes apart (ds_read2_b64).
-    constexpr int LSTEP = LAZY ? 2 * M3 : M3;
-    const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sa + buf * NPAIR * 4 + li * LSTEP);
-    const uint32_t lb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sb + buf * NPAIR * 4 + lj * LSTEP);
+    // the two pieces of an operand are 16 columns = 128 bytes apart (ds_read2_b64)
+    const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sa + buf * NPAIR * 4 + li * M3);
+    const uint32_t lb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sb + buf * NPAIR * 4 + lj * M3);
     static_assert(RBG % 4 == 0 && M3 == 2, "four rows per trip, offsets in units of 8 bytes");
     // One 2 x 2-limb product into the three columns of an output (ONE), or the products of both pieces of the i operand
-    // with one piece of the j operand into two outputs (BOTH).  FX3_*: carrying, 96-bit columns c + h 2^64; FX3L_*: lazy,
-    // plain 64-bit column sums.
+    // with one piece of the j operand into two outputs (BOTH): carrying, 96-bit columns c + h 2^64.
 #define FX3_P(C, H, X, Y) "v_mad_u64_u32 %" #C ", vcc, %" #X ", %" #Y ", %" #C "\n\tv_addc_co_u32 %" #H ", vcc, 0, %" #H ", vcc\n\t"
-#define FX3_L(C, X, Y) "v_mad_u64_u32 %" #C ", vcc, %" #X ", %" #Y ", %" #C "\n\t"
 #define FX3_MAC_BOTH(o0, o1, a0x, a0y, a1x, a1y, bx, by)                                                                                   \
   asm volatile(FX3_P(0, 6, 12, 16) FX3_P(3, 9, 14, 16) FX3_P(1, 7, 12, 17) FX3_P(4, 10, 14, 17) FX3_P(1, 7, 13, 16) FX3_P(4, 10, 15, 16)   \
                  FX3_P(2, 8, 13, 17) FX3_P(5, 11, 15, 17)                                                                                  \
@@ -3902,17 +3895,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
 #define FX3_MAC_ONE(o0, ax, ay, bx, by)                                                                                                    \
   asm volatile(FX3_P(0, 3, 6, 8) FX3_P(1, 4, 6, 9) FX3_P(1, 4, 7, 8) FX3_P(2, 5, 7, 9)                                                     \
                : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2]), "+v"(h[o0][0]), "+v"(h[o0][1]), "+v"(h[o0][2])                            \
-               : "v"(ax), "v"(ay), "v"(bx), "v"(by)                                                                                        \
-               : "vcc")
-#define FX3L_MAC_BOTH(o0, o1, a0x, a0y, a1x, a1y, bx, by)                                                                                  \
-  asm volatile(FX3_L(0, 6, 10) FX3_L(3, 8, 10) FX3_L(1, 6, 11) FX3_L(4, 8, 11) FX3_L(1, 7, 10) FX3_L(4, 9, 10) FX3_L(2, 7, 11)             \
-                 FX3_L(5, 9, 11)                                                                                                           \
-               : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2]), "+v"(c[o1][0]), "+v"(c[o1][1]), "+v"(c[o1][2])                            \
-               : "v"(a0x), "v"(a0y), "v"(a1x), "v"(a1y), "v"(bx), "v"(by)                                                                  \
-               : "vcc")
-#define FX3L_MAC_ONE(o0, ax, ay, bx, by)                                                                                                   \
-  asm volatile(FX3_L(0, 3, 5) FX3_L(1, 3, 6) FX3_L(1, 4, 5) FX3_L(2, 4, 6)                                                                 \
-               : "+v"(c[o0][0]), "+v"(c[o0][1]), "+v"(c[o0][2])                                                                            \
                : "v"(ax), "v"(ay), "v"(bx), "v"(by)                                                                                        \
                : "vcc")
     // the products of one row for the quadrants of MASK
@@ -3935,7 +3917,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
   else                                                                                                                                     \
     ONE(0, va.x, va.y, vb.x, vb.y);
 #define FX3_MACS(va, vb) FX3_QUADRANTS(FX3_MAC_BOTH, FX3_MAC_ONE, va, vb)
-#define FX3L_MACS(va, vb) FX3_QUADRANTS(FX3L_MAC_BOTH, FX3L_MAC_ONE, va, vb)
     // The reads of row r + 1 are issued before the products of row r: two register sets, each handed from the
     // statement that issues its reads to the statement that waits for them without the compiler touching it in between.
     // (With half of the LDS reads the whole product would be 5 % faster: profiles/r06_syrk_lds_experiment.txt.)
@@ -3946,91 +3927,40 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
                : "+v"(wa), "+v"(wb), "=&v"(ra), "=&v"(rb)                                                                                  \
                : "v"(xa), "v"(xb)                                                                                                          \
                : "memory")
-    // LAZY: wait for the set (wa, wb), then issue the two 128-bit reads of row ROW of the trip into (ra, rb); the row's
-    // byte offset (256 ROW, at most 32 rows: 8192) is the instruction's immediate, so a trip needs no address arithmetic
-#define FX3L_NEXT(wa, wb, ra, rb, ROW)                                                                                                     \
-  asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %2, %4 offset:%6\n\tds_read_b128 %3, %5 offset:%6"                                   \
-               : "+v"(wa), "+v"(wb), "=&v"(ra), "=&v"(rb)                                                                                  \
-               : "v"(xa), "v"(xb), "n"((ROW) * 256)                                                                                        \
-               : "memory")
-#define FX3L_ROWS2(R)                                                                                                                      \
-  FX3L_NEXT(a0, b0, a1, b1, (R) + 1);                                                                                                      \
-  FX3L_MACS(a0, b0)                                                                                                                        \
-  FX3L_NEXT(a1, b1, a0, b0, (R) + 2);                                                                                                      \
-  FX3L_MACS(a1, b1)
-#define FX3L_ROWS8(R) FX3L_ROWS2(R) FX3L_ROWS2((R) + 2) FX3L_ROWS2((R) + 4) FX3L_ROWS2((R) + 6)
     u32x4 a0, b0, a1, b1;
-    if constexpr(LAZY)
-      {
-        // TRIP rows per trip of the loop (SDPB_SYRK3_LAZY_TRIP: 8, 16 or 32; a whole pass where it divides RBG)
-        constexpr int TRIP = (RBG % SDPB_SYRK3_LAZY_TRIP == 0) ? SDPB_SYRK3_LAZY_TRIP : 8;
-        static_assert(RBG % 8 == 0 && (TRIP == 8 || TRIP == 16 || TRIP == 32) && RBG * 256 < 65536, "whole trips, the offsets fit 16 bits");
-        {
-          const uint32_t xa = la, xb = lb;
-          asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
-        }
+    {
+      const uint32_t xa = la, xb = lb;
+      asm volatile("ds_read2_b64 %0, %2 offset0:0 offset1:16\n\tds_read2_b64 %1, %3 offset0:0 offset1:16" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
+    }
 #pragma unroll 1
-        for(int rr = 0; rr < RBG; rr += TRIP)
-          {
-            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words (folded away when a trip is the pass)
-            // the last read of the last trip is row RBG: the first row of the other buffer (or, behind the last buffer,
-            // the 64 words sa / sb carry for it: 16 li + 16 <= 256 bytes); the data is dropped
-            FX3L_ROWS8(0)
-            if constexpr(TRIP >= 16)
-              {
-                FX3L_ROWS8(8)
-              }
-            if constexpr(TRIP >= 32)
-              {
-                FX3L_ROWS8(16)
-                FX3L_ROWS8(24)
-              }
-          }
-      }
-    else
+    for(int rr = 0; rr < RBG; rr += 4)
       {
-        {
-          const uint32_t xa = la, xb = lb;
-          asm volatile("ds_read2_b64 %0, %2 offset0:0 offset1:16\n\tds_read2_b64 %1, %3 offset0:0 offset1:16" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
-        }
-#pragma unroll 1
-        for(int rr = 0; rr < RBG; rr += 4)
-          {
-            const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
-            FX3_NEXT(a0, b0, a1, b1, 32, 48);
-            FX3_MACS(a0, b0)
-            FX3_NEXT(a1, b1, a0, b0, 64, 80);
-            FX3_MACS(a1, b1)
-            FX3_NEXT(a0, b0, a1, b1, 96, 112);
-            FX3_MACS(a0, b0)
-            // row rr + 4; past the last row of the pass this reads the first row of the other buffer (or, behind sb, LDS
-            // that is not ours): the data is dropped
-            FX3_NEXT(a1, b1, a0, b0, 128, 144);
-            FX3_MACS(a1, b1)
-          }
+        const uint32_t xa = la + rr * 256, xb = lb + rr * 256; // a staged row is 64 words
+        FX3_NEXT(a0, b0, a1, b1, 32, 48);
+        FX3_MACS(a0, b0)
+        FX3_NEXT(a1, b1, a0, b0, 64, 80);
+        FX3_MACS(a1, b1)
+        FX3_NEXT(a0, b0, a1, b1, 96, 112);
+        FX3_MACS(a0, b0)
+        // row rr + 4; past the last row of the pass this reads the first row of the other buffer (or, behind sb, LDS
+        // that is not ours): the data is dropped
+        FX3_NEXT(a1, b1, a0, b0, 128, 144);
+        FX3_MACS(a1, b1)
       }
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(b0)::"memory");
-#undef FX3L_ROWS8
-#undef FX3L_ROWS2
-#undef FX3L_NEXT
 #undef FX3_NEXT
-#undef FX3L_MACS
 #undef FX3_MACS
 #undef FX3_QUADRANTS
-#undef FX3L_MAC_ONE
-#undef FX3L_MAC_BOTH
 #undef FX3_MAC_ONE
 #undef FX3_MAC_BOTH
 #undef FX3_P
-#undef FX3_L
 #endif
       }
     else
       {
-        // column x of the tile sits at word M3 x of a staged row: the lane's two pieces are 16 columns apart -- or, in the
-        // tile column order of the lazy-carry image (fx_col_slot), neighbours: columns l and l + 16 in slots 2 l and 2 l + 1
-        constexpr int LSTEP = LAZY ? 2 * M3 : M3, SECOND = LAZY ? M3 : 16 * M3;
-        const uint32_t *pa = sa + buf * NPAIR * 4 + li * LSTEP, *pb = sb + buf * NPAIR * 4 + lj * LSTEP;
+        // column x of the tile sits at word M3 x of a staged row: the lane's two pieces are 16 columns apart
+        constexpr int SECOND = 16 * M3;
+        const uint32_t *pa = sa + buf * NPAIR * 4 + li * M3, *pb = sb + buf * NPAIR * 4 + lj * M3;
 #pragma unroll SDPB_SYRK2_UNROLL
         for(int rr = 0; rr < RBG; ++rr)
           {
@@ -4041,23 +3971,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
               piece_load<M3>(pa + rr * ROWW + SECOND, a1);
             if constexpr((MASK & 12) != 0)
               piece_load<M3>(pb + rr * ROWW + SECOND, b1);
-            if constexpr(LAZY)
-              {
-                auto lazy = [&](const uint32_t (&x)[M3], const uint32_t (&y)[M3], uint64_t (&cs)[2 * M3 - 1]) {
-                  cs[0] += (uint64_t)x[0] * y[0];
-                  cs[1] += (uint64_t)x[0] * y[1] + (uint64_t)x[1] * y[0];
-                  cs[2] += (uint64_t)x[1] * y[1];
-                };
-                lazy(a0, b0, c[0]);
-                if constexpr((MASK & 2) != 0)
-                  lazy(a1, b0, c[1]);
-                if constexpr((MASK & 4) != 0)
-                  lazy(a0, b1, c[2]);
-                if constexpr((MASK & 8) != 0)
-                  lazy(a1, b1, c[3]);
-              }
-            else
-              {
             SyrkColumns<M3, 0>::run(a0, b0, c[0], h[0]);
             if constexpr((MASK & 2) != 0)
               SyrkColumns<M3, 0>::run(a1, b0, c[1], h[1]);
@@ -4065,7 +3978,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
               SyrkColumns<M3, 0>::run(a0, b1, c[2], h[2]);
             if constexpr((MASK & 8) != 0)
               SyrkColumns<M3, 0>::run(a1, b1, c[3], h[3]);
-              }
           }
       }
   };
@@ -4082,38 +3994,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
             cc[o][k] = 0;
             hh[o][k] = 0;
           }
-#pragma unroll
-      for(int o = 0; o < 4; ++o)
-#pragma unroll
-        for(int k = 0; k < 2 * M3 - 1; ++k)
-          dd[o][k] = 0;
-      // LAZY: column k of an output absorbs products < 2^56, two of them per row in the middle column.  Nothing is carried
-      // from column to column during the sweep: the HIGH WORD of a column is moved to a second sum of the same column (an
-      // add, an add-with-carry and a move per column: no 64-bit shifts, no masks) -- the middle column every 64 rows (it is
-      // < 2^32 + 64 * 2 * 2^56 < 2^64 by then), the outer ones every 128 rows.  (First version of the round: carries from
-      // column to column every 64 rows, 15 instructions per output with three 64-bit shifts; profiles/r06_syrk_light_carry.txt)
-      auto carry_columns = [&](bool all) __attribute__((always_inline)) {
-        if constexpr(LAZY)
-          {
-#pragma unroll
-            for(int o = 0; o < 4; ++o)
-              {
-                dd[o][1] += cc[o][1] >> 32;
-                cc[o][1] &= 0xffffffffull;
-              }
-            if(all)
-              {
-#pragma unroll
-                for(int o = 0; o < 4; ++o)
-                  {
-                    dd[o][0] += cc[o][0] >> 32;
-                    cc[o][0] &= 0xffffffffull;
-                    dd[o][2] += cc[o][2] >> 32;
-                    cc[o][2] &= 0xffffffffull;
-                  }
-              }
-          }
-      };
       if(prod > prod_begin)
         __syncthreads(); // every wavefront has left the last pass of the previous sweep (and what it over-fetched has landed)
       fetch(prod, row_begin, 0);
@@ -4123,15 +4003,11 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
       // the same registers from block to block
       auto sweep = [&](auto mask_c) __attribute__((always_inline)) {
         int buf = 0;
-        unsigned pass = 0;
         for(unsigned r0 = row_begin; r0 < row_end; r0 += RBG)
           {
             // (after the last block of the sweep: a block that exists, staged and never read)
             fetch(prod, r0 + RBG < row_end ? r0 + RBG : row_begin, buf ^ 1);
             rows(mask_c, buf, cc, hh);
-            ++pass;
-            if(LAZY && (pass & 1u) == 0) // every second pass
-              carry_columns((pass & 3u) == 0);
             store(buf ^ 1);
             __syncthreads(); // the rows of the next pass have landed in LDS
             buf ^= 1;
@@ -4154,19 +4030,6 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
 #pragma unroll
           for(int k = 0; k < A3; ++k)
             g[k] = 0;
-          if constexpr(LAZY)
-            {
-              // sum_k (c_k + d_k 2^32) 2^(28 k): below 2^124 (fewer than 2^12 rows of products < 2^112): 4 words
-              unsigned __int128 v = 0;
-#pragma unroll
-              for(int k = 0; k < 2 * M3 - 1; ++k)
-                v += ((unsigned __int128)cc[o][k] + ((unsigned __int128)dd[o][k] << 32)) << (T5_LB * k);
-              g[0] = (uint32_t)v;
-              g[1] = (uint32_t)(v >> 32);
-              g[2] = (uint32_t)(v >> 64);
-              g[3] = (uint32_t)(v >> 96);
-            }
-          else
           syrk_fold<M3, A3>(g, cc[o], hh[o]);
           const size_t at = (size_t)tile * 1024 + (size_t)(li + 16 * (o & 1)) + (size_t)(lj + 16 * (o >> 1)) * 32; // tile-packed
 #pragma unroll
@@ -4176,7 +4039,327 @@ __global__ void __launch_bounds__(WG, SDPB_SYRK3_WAVES)
     }
 }
 
-// The row splits of k_syrk_fx3 added in place (into the planes of split 0), one lane per (product, output element): the
+// ---- Toom-5 x two Karatsuba levels with lazy carries: the product of the 81-plane image (fx_toom5k) ------------------
+// Each of the 27 products of two-limb pieces (x0, x1)(y0, y1) is three ONE-limb products instead of four: with
+// xm = x0 + x1 stored in the image, x y = s0 + (sm - s0 - s1) 2^28 + s1 2^56 for the row sums s0 = sum x0 y0, s1 = sum x1 y1,
+// sm = sum xm ym -- 81 multiply-adds per row pair.  A product is therefore three SUB-SWEEPS over the split's rows
+// (t = x0, x1, xm: image plane 3 product + t), and a sub-sweep is a plain one-word syrk.
+// A workgroup is ONE wavefront and owns one (32 x 32 tile, row split, product).  Lane (li, lj) = (tid & 7, tid >> 3) owns the
+// 4 x 4 outputs (i0 + 8 p, j0 + 8 q), i0 = 32 ti + li, j0 = 32 tj + lj: in the tile column order (fx_col_slot) its four words of
+// an operand are the 16 bytes at 16 li (16 lj) of the staged 128-byte row, so a row costs a lane two ds_read_b128 and 16
+// v_mad_u64_u32, c[p][q] += a[p] b[q] -- the same LDS bytes and instructions per multiply-add as two 2 x 2-limb products
+// per lane, for 3/4 of the multiply-adds.  The addresses of a read fall on at most 8 distinct 16-byte slots of one
+// 128-byte span: no bank conflicts.  8 x 8 sub-blocks without outputs are skipped workgroup-wide: q > p on a diagonal
+// tile, and the row groups p >= 2 of a last tile row with at most 16 rows inside N.
+// Carries: a column sum is a plain 64-bit integer; its HIGH WORD is moved to a second sum every SYRK5_CARRY_ROWS_XM rows
+// (t = xm: words <= 2^29 - 2) or every SYRK5_CARRY_ROWS_X rows (x0, x1: words < 2^28), see the static_asserts.  When a
+// sub-sweep ends the owning lane adds its term s0 (1 - 2^28), s1 (2^56 - 2^28) or sm 2^28 (mod 2^128) into the product's
+// planes by its own read-modify-write (t = 0 stores), so the planes hold the same product sums, at the same tile-packed
+// positions, as one 2 x 2-limb sweep would have left: k_syrk3_sum_splits and k_syrk5_finish do not know the difference.
+#ifndef SDPB_SYRK5_ROWS
+#define SDPB_SYRK5_ROWS 16 // rows staged per pass (16 or 32).  16: 8 KB of LDS, 16 workgroups per CU; 32 leaves room for 10 and is 6 % slower (profiles/syrk_k2_isa.txt)
+#endif
+constexpr int SYRK5_WG = 64;
+constexpr uint32_t T5_XM_MAX = 2 * T5_MASK; // xm = x0 + x1 <= 2^29 - 2
+constexpr unsigned SYRK5_CARRY_ROWS_XM = 64, SYRK5_CARRY_ROWS_X = 128;
+static_assert(((unsigned __int128)1 << 32) + (unsigned __int128)SYRK5_CARRY_ROWS_XM * T5_XM_MAX * T5_XM_MAX < ((unsigned __int128)1 << 64),
+              "a column of xm products: what a carry leaves (< 2^32) plus 64 rows stays below 2^64");
+static_assert(((unsigned __int128)1 << 32) + (unsigned __int128)SYRK5_CARRY_ROWS_X * T5_MASK * T5_MASK < ((unsigned __int128)1 << 64),
+              "a column of x0 or x1 products: what a carry leaves plus 128 rows stays below 2^64");
+// one-wave workgroups a CU holds: two operands x two staging buffers x 128 bytes per row of its 160 KB of LDS, and
+// four wavefronts per SIMD at up to 128 registers
+constexpr int syrk5_wg_per_cu(int rows_per_pass) { return 160 * 1024 / (4 * 128 * rows_per_pass) < 16 ? 160 * 1024 / (4 * 128 * rows_per_pass) : 16; }
+// The arithmetic of one lane, shared by the kernel and by tests/shim/syrk_k2_bounds_check.cpp (which runs it at the bounds of
+// the image words, where no real image gets): c the column sums of the 4 x 4 outputs, d the high words taken out of them.
+template <int PN, bool DIAG> MW_HD void syrk5k2_mac_row(uint64_t (&c)[4][4], const uint32_t (&a)[4], const uint32_t (&b)[4])
+{
+#pragma unroll
+  for(int p = 0; p < PN; ++p)
+#pragma unroll
+    for(int q = 0; q < 4; ++q)
+      if(!DIAG || q <= p)
+        c[p][q] += (uint64_t)a[p] * b[q];
+}
+MW_HD void syrk5k2_carry(uint64_t (&c)[4][4], uint64_t (&d)[4][4])
+{
+#pragma unroll
+  for(int p = 0; p < 4; ++p)
+#pragma unroll
+    for(int q = 0; q < 4; ++q)
+      {
+        d[p][q] += c[p][q] >> 32;
+        c[p][q] &= 0xffffffffull;
+      }
+}
+// after every pass of RBG rows of sub-sweep t; `since` counts the rows since the last carry
+template <int RBG> MW_HD void syrk5k2_pass_end(int t, unsigned &since, uint64_t (&c)[4][4], uint64_t (&d)[4][4])
+{
+  static_assert(SYRK5_CARRY_ROWS_XM % RBG == 0 && SYRK5_CARRY_ROWS_X % RBG == 0, "the carry cadences are whole passes");
+  since += RBG;
+  if(since >= (t == 2 ? SYRK5_CARRY_ROWS_XM : SYRK5_CARRY_ROWS_X))
+    {
+      syrk5k2_carry(c, d);
+      since = 0;
+    }
+}
+// the term of sub-sweep t in V = s0 + (sm - s0 - s1) 2^28 + s1 2^56, mod 2^128 (V itself is below 2^128 while a split has
+// fewer than 2^16 rows; below 2^124 with the 2560 rows of a planned split)
+MW_HD unsigned __int128 syrk5k2_term(int t, uint64_t c, uint64_t d)
+{
+  const unsigned __int128 s = (unsigned __int128)c + ((unsigned __int128)d << 32);
+  return t == 0 ? s - (s << T5_LB) : t == 1 ? (s << (2 * T5_LB)) - (s << T5_LB) : s << T5_LB;
+}
+
+template <int FX, int RBG>
+__global__ void __launch_bounds__(SYRK5_WG)
+  k_syrk5_k2(const uint32_t *__restrict__ fx_in, size_t fx_stride, unsigned nrows, int N, uint32_t *acc, size_t acc_stride,
+             const uint32_t *tile_list, int ntile, int nsplit, unsigned rows_per_split, int gsplit)
+{
+  // gsplit = 27 (9, 1): a workgroup takes one product (the three of a point, all 27) of its (tile, row split)
+  constexpr int A3 = fx_part_limbs<FX>(), NPROD = fx_nprod<FX>();
+  static_assert(fx_toom5k<FX>() && A3 == 5 && (RBG == 16 || RBG == 32), "one-word planes of the lazy-carry image; whole 16-byte units per lane and pass");
+  // a staged row = the words of the tile's 32 slots = 8 16-byte units; a pass stages RBG rows of each operand
+  constexpr int UNITS = RBG * 8, GL = UNITS / SYRK5_WG;
+  const uint32_t *fx = (const uint32_t *)__builtin_assume_aligned(fx_in, 4);
+  const int nitem = ntile * nsplit * gsplit, per = (nitem + 7) / 8;
+  const int item = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+  if((int)(blockIdx.x / 8) >= per || item >= nitem)
+    return;
+  // items that follow each other share the rows and the product, i.e. the operand panels of neighbouring tiles
+  const int sg = item / ntile, tile = item % ntile, split = sg / gsplit;
+  const int prod_begin = (sg % gsplit) * (NPROD / gsplit), prod_end = prod_begin + NPROD / gsplit;
+  const unsigned row_begin = (unsigned)split * rows_per_split;
+  const unsigned row_end = (row_begin + rows_per_split < nrows && split + 1 < nsplit) ? row_begin + rows_per_split : nrows;
+  acc += (size_t)split * NPROD * A3 * acc_stride;
+  const uint32_t tt = tile_list[tile];
+  const int ti = (int)(tt >> 16), tj = (int)(tt & 0xffffu);
+  const int li = threadIdx.x & 7, lj = threadIdx.x >> 3;
+  const int i0 = ti * 32 + li, j0 = tj * 32 + lj;
+  // the row loop's instantiation (workgroup-uniform): bit 0: diagonal tile, bit 1: at most 16 of the tile's rows inside N
+  const int variant = (ti == tj ? 1 : 0) | (ti * 32 + 16 < N ? 0 : 2);
+  __shared__ __attribute__((aligned(16))) uint32_t sa[2 * UNITS * 4];
+  __shared__ __attribute__((aligned(16))) uint32_t sb[2 * UNITS * 4];
+  uint64_t cc[4][4], dd[4][4];
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool DIRECT = true; // (the host path of the emulation build stages through registers)
+#else
+  constexpr bool DIRECT = false;
+#endif
+  // Staging: the image is padded with zero rows to a multiple of 32 and every image row to whole tiles of zero-padded slots
+  // (fx_image_stride, fx_row_slots), and a split begins at a multiple of 32 rows: a pass is the same per-lane offsets from a
+  // workgroup-uniform base, inside the plane, without bounds checks.
+  const size_t NS = fx_row_slots<FX>((size_t)N);
+  uint32_t va[DIRECT ? 1 : GL][4], vb[DIRECT ? 1 : GL][4];
+  uint32_t offa[GL], offb[GL];
+#pragma unroll
+  for(int g = 0; g < GL; ++g)
+    {
+      const int e = threadIdx.x + g * SYRK5_WG;
+      const int unit = e % 8, rr = e / 8;
+      offa[g] = (uint32_t)((size_t)rr * NS + ti * 32 + 4 * unit);
+      offb[g] = (uint32_t)((size_t)rr * NS + tj * 32 + 4 * unit);
+    }
+  auto fetch = [&](int plane, unsigned r0, int into) __attribute__((always_inline)) {
+    const uint32_t *base = fx + (size_t)plane * fx_stride + (size_t)r0 * NS;
+#pragma unroll
+    for(int g = 0; g < GL; ++g)
+      {
+        if constexpr(DIRECT)
+          {
+#if defined(__HIP_DEVICE_COMPILE__)
+            const int wbase = (into * UNITS + g * SYRK5_WG) * 4; // the wavefront's 64 units, lane by lane
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(base + offa[g]),
+                                             (__attribute__((address_space(3))) void *)(sa + wbase), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(base + offb[g]),
+                                             (__attribute__((address_space(3))) void *)(sb + wbase), 16, 0, 0);
+#endif
+          }
+        else
+          {
+#pragma unroll
+            for(int l = 0; l < 4; ++l)
+              {
+                va[g][l] = base[offa[g] + l];
+                vb[g][l] = base[offb[g] + l];
+              }
+          }
+      }
+  };
+  auto store = [&](int buf) __attribute__((always_inline)) {
+    if constexpr(!DIRECT)
+      {
+#pragma unroll
+        for(int g = 0; g < GL; ++g)
+          {
+            const int e = threadIdx.x + g * SYRK5_WG;
+            piece_store<4>(sa + (buf * UNITS + e) * 4, va[g]);
+            piece_store<4>(sb + (buf * UNITS + e) * 4, vb[g]);
+          }
+      }
+  };
+  // what was staged has landed in LDS and nobody reads the other buffer any more.  The workgroup is one wavefront: on the
+  // device that is its own outstanding global_load_lds (the row loop's reads are waited for where they are issued); the
+  // emulation build runs the lanes as fibers that meet here.
+  auto landed = [&]() __attribute__((always_inline)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
+    __syncthreads();
+#endif
+  };
+  // the RBG staged rows of one pass
+  auto rows = [&](auto variant_c, int buf) __attribute__((always_inline)) {
+    constexpr int V = decltype(variant_c)::value;
+    constexpr int PN = (V & 2) ? 2 : 4;
+    constexpr bool DIAG = (V & 1) != 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // LDS reads and multiply-adds as one asm statement each per row, the reads invisible to the compiler's wait-count pass
+    // (which would drain the global_load_lds of the NEXT pass before the first read of this one; those land in the other
+    // buffer).  The reads of row r + 1 are issued before the products of row r: two register sets, each handed from the
+    // statement that issues its reads to the statement that waits for them.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const uint32_t xa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sa + buf * UNITS * 4 + li * 4);
+    const uint32_t xb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(sb + buf * UNITS * 4 + lj * 4);
+    // operands: %(4 p + q) = c[p][q], %(16 + p) = a[p], %(20 + q) = b[q]
+#define K2_L(C, A, B) "v_mad_u64_u32 %" #C ", vcc, %" #A ", %" #B ", %" #C "\n\t"
+#define K2_FULL                                                                                                                            \
+  K2_L(0, 16, 20) K2_L(1, 16, 21) K2_L(2, 16, 22) K2_L(3, 16, 23) K2_L(4, 17, 20) K2_L(5, 17, 21) K2_L(6, 17, 22) K2_L(7, 17, 23)          \
+  K2_L(8, 18, 20) K2_L(9, 18, 21) K2_L(10, 18, 22) K2_L(11, 18, 23) K2_L(12, 19, 20) K2_L(13, 19, 21) K2_L(14, 19, 22) K2_L(15, 19, 23)
+#define K2_DIAG                                                                                                                            \
+  K2_L(0, 16, 20) K2_L(4, 17, 20) K2_L(5, 17, 21) K2_L(8, 18, 20) K2_L(9, 18, 21) K2_L(10, 18, 22) K2_L(12, 19, 20) K2_L(13, 19, 21)       \
+  K2_L(14, 19, 22) K2_L(15, 19, 23)
+#define K2_HALF K2_L(0, 16, 20) K2_L(1, 16, 21) K2_L(2, 16, 22) K2_L(3, 16, 23) K2_L(4, 17, 20) K2_L(5, 17, 21) K2_L(6, 17, 22) K2_L(7, 17, 23)
+#define K2_HALF_DIAG K2_L(0, 16, 20) K2_L(4, 17, 20) K2_L(5, 17, 21)
+#define K2_MACS(va, vb)                                                                                                                    \
+  if constexpr(V == 0)                                                                                                                     \
+    {                                                                                                                                      \
+      K2_ASM(K2_FULL, va, vb)                                                                                                              \
+    }                                                                                                                                      \
+  else if constexpr(V == 1)                                                                                                                \
+    {                                                                                                                                      \
+      K2_ASM(K2_DIAG, va, vb)                                                                                                              \
+    }                                                                                                                                      \
+  else if constexpr(V == 2)                                                                                                                \
+    {                                                                                                                                      \
+      K2_ASM(K2_HALF, va, vb)                                                                                                              \
+    }                                                                                                                                      \
+  else                                                                                                                                     \
+    {                                                                                                                                      \
+      K2_ASM(K2_HALF_DIAG, va, vb)                                                                                                         \
+    }
+#define K2_ASM(MACS, va, vb)                                                                                                               \
+  asm volatile(MACS                                                                                                                        \
+               : "+v"(cc[0][0]), "+v"(cc[0][1]), "+v"(cc[0][2]), "+v"(cc[0][3]), "+v"(cc[1][0]), "+v"(cc[1][1]), "+v"(cc[1][2]),           \
+                 "+v"(cc[1][3]), "+v"(cc[2][0]), "+v"(cc[2][1]), "+v"(cc[2][2]), "+v"(cc[2][3]), "+v"(cc[3][0]), "+v"(cc[3][1]),           \
+                 "+v"(cc[3][2]), "+v"(cc[3][3])                                                                                            \
+               : "v"(va.x), "v"(va.y), "v"(va.z), "v"(va.w), "v"(vb.x), "v"(vb.y), "v"(vb.z), "v"(vb.w)                                    \
+               : "vcc");
+    // wait for the set (wa, wb) that is in flight, then issue the two 128-bit reads of row ROW of the pass into (ra, rb); the
+    // row's byte offset (128 ROW < 4096) is the instruction's immediate
+#define K2_NEXT(wa, wb, ra, rb, ROW)                                                                                                       \
+  asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %2, %4 offset:%6\n\tds_read_b128 %3, %5 offset:%6"                                   \
+               : "+v"(wa), "+v"(wb), "=&v"(ra), "=&v"(rb)                                                                                  \
+               : "v"(xa), "v"(xb), "n"((ROW) * 128)                                                                                        \
+               : "memory");
+#define K2_ROWS2(R) K2_NEXT(a0, b0, a1, b1, (R) + 1) K2_MACS(a0, b0) K2_NEXT(a1, b1, a0, b0, (R) + 2) K2_MACS(a1, b1)
+#define K2_ROWS8(R) K2_ROWS2(R) K2_ROWS2((R) + 2) K2_ROWS2((R) + 4) K2_ROWS2((R) + 6)
+    u32x4 a0, b0, a1, b1;
+    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(a0), "=&v"(b0) : "v"(xa), "v"(xb) : "memory");
+    K2_ROWS8(0)
+    if constexpr(RBG == 32)
+      {
+        K2_ROWS8(8)
+        K2_ROWS8(16)
+      }
+    K2_ROWS2(RBG - 8)
+    K2_ROWS2(RBG - 6)
+    K2_ROWS2(RBG - 4)
+    // the last two rows: nothing is read past the pass
+    K2_NEXT(a0, b0, a1, b1, RBG - 1)
+    K2_MACS(a0, b0)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a1), "+v"(b1)::"memory");
+    K2_MACS(a1, b1)
+#undef K2_ROWS8
+#undef K2_ROWS2
+#undef K2_NEXT
+#undef K2_ASM
+#undef K2_MACS
+#undef K2_HALF_DIAG
+#undef K2_HALF
+#undef K2_DIAG
+#undef K2_FULL
+#undef K2_L
+#else
+    const uint32_t *pa = sa + buf * UNITS * 4 + li * 4, *pb = sb + buf * UNITS * 4 + lj * 4;
+    for(int rr = 0; rr < RBG; ++rr)
+      {
+        uint32_t a[4], b[4];
+        piece_load<4>(pa + rr * 32, a);
+        piece_load<4>(pb + rr * 32, b);
+        syrk5k2_mac_row<PN, DIAG>(cc, a, b);
+      }
+#endif
+  };
+  for(int prod = prod_begin; prod < prod_end; ++prod)
+    for(int t = 0; t < 3; ++t)
+      {
+        const int plane = 3 * prod + t;
+#pragma unroll
+        for(int p = 0; p < 4; ++p)
+#pragma unroll
+          for(int q = 0; q < 4; ++q)
+            cc[p][q] = dd[p][q] = 0;
+        unsigned since = 0;
+        landed(); // every lane has left the last pass of the previous sub-sweep (and what it over-fetched has landed)
+        fetch(plane, row_begin, 0);
+        store(0);
+        landed();
+        // the row blocks of the sub-sweep; the instantiation is chosen outside the loop, so that the sums stay in the same
+        // registers from block to block
+        auto sweep = [&](auto variant_c) __attribute__((always_inline)) {
+          int buf = 0;
+          for(unsigned r0 = row_begin; r0 < row_end; r0 += RBG)
+            {
+              // (after the last block of the sub-sweep: a block that exists, staged and never read)
+              fetch(plane, r0 + RBG < row_end ? r0 + RBG : row_begin, buf ^ 1);
+              rows(variant_c, buf);
+              syrk5k2_pass_end<RBG>(t, since, cc, dd);
+              store(buf ^ 1);
+              landed();
+              buf ^= 1;
+            }
+        };
+        switch(variant)
+          {
+          case 0: sweep(std::integral_constant<int, 0>()); break;
+          case 1: sweep(std::integral_constant<int, 1>()); break;
+          case 2: sweep(std::integral_constant<int, 2>()); break;
+          default: sweep(std::integral_constant<int, 3>()); break;
+          }
+#pragma unroll
+        for(int p = 0; p < 4; ++p)
+#pragma unroll
+          for(int q = 0; q < 4; ++q)
+            {
+              const int i = i0 + 8 * p, j = j0 + 8 * q;
+              if(i >= N || j > i)
+                continue;
+              uint32_t *o = acc + (size_t)(prod * A3) * acc_stride + (size_t)tile * 1024 + (size_t)(li + 8 * p) + (size_t)(lj + 8 * q) * 32; // tile-packed
+              unsigned __int128 v = syrk5k2_term(t, cc[p][q], dd[p][q]);
+              if(t > 0)
+                v += (unsigned __int128)o[0] | ((unsigned __int128)o[acc_stride] << 32) | ((unsigned __int128)o[2 * acc_stride] << 64)
+                     | ((unsigned __int128)o[3 * acc_stride] << 96);
+              else
+                o[4 * acc_stride] = 0;
+              o[0] = (uint32_t)v;
+              o[acc_stride] = (uint32_t)(v >> 32);
+              o[2 * acc_stride] = (uint32_t)(v >> 64);
+              o[3 * acc_stride] = (uint32_t)(v >> 96);
+            }
+      }
+}
+
+// The row splits of k_syrk_fx3 / k_syrk5_k2 added in place (into the planes of split 0), one lane per (product, output element): the
 // 16 x 105 planes of C4 read once by 21 x N^2 / 2 lanes at full occupancy instead of by the N^2 / 2 lanes of
 // k_syrk4_finish with their 196 registers (that kernel alone took 3.98 ms per launch with 16 splits; product + sum +
 // finish: 98.5 -> 95.6 ms); A3 limbs hold the sum over ALL rows (< 2^32 of them).
@@ -4216,15 +4399,16 @@ constexpr uint32_t inv_mod_2_32(uint32_t c)
   return x;
 }
 constexpr int T5_Z = 10; // limbs of the signed integers of the interpolation
-// the evaluated value lo + hi 2^55 of a point from its two stored halves (limbs of 28 bits), as four 32-bit words
+// the evaluated value lo + hi 2^55 of a point from the limbs x0, x1 (28 bits) of its two stored halves (planes 9 g + 3 u + t,
+// u = lo, hi and t = x0, x1), as four 32-bit words
 MW_HD void toom5_value(const uint32_t *fx, size_t fx_stride, int point, size_t e, uint32_t (&w)[4])
 {
-  const PiecePair lo = *reinterpret_cast<const PiecePair *>(fx + ((size_t)(3 * point + 0) * fx_stride + e) * 2);
-  const PiecePair hi = *reinterpret_cast<const PiecePair *>(fx + ((size_t)(3 * point + 1) * fx_stride + e) * 2);
-  w[0] = lo.w[0] | (lo.w[1] << 28);
-  w[1] = (lo.w[1] >> 4) | (hi.w[0] << 23);
-  w[2] = (hi.w[0] >> 9) | (hi.w[1] << 19);
-  w[3] = hi.w[1] >> 13;
+  const uint32_t lo0 = fx[(size_t)(9 * point + 0) * fx_stride + e], lo1 = fx[(size_t)(9 * point + 1) * fx_stride + e];
+  const uint32_t hi0 = fx[(size_t)(9 * point + 3) * fx_stride + e], hi1 = fx[(size_t)(9 * point + 4) * fx_stride + e];
+  w[0] = lo0 | (lo1 << 28);
+  w[1] = (lo1 >> 4) | (hi0 << 23);
+  w[2] = (hi0 >> 9) | (hi1 << 19);
+  w[3] = hi1 >> 13;
 }
 // Stage 1 (the shape of k_fx_colsum2): workgroup (x, y) sums row slice y of 64 columns of the five groups a0, p(1), p(2),
 // 16 p(1/2), a4 -- enough to recover the column sums of all five pieces -- into partial[y]; element (slice, u, k, n), u < 5,

@@ -923,7 +923,7 @@ public:
     ss << (first ? "" : ", ") << "\"kernel.k_syrk_fx.ms\": " << syrk_kernel_ms_ << ", \"kernel.k_syrk_fx.launches\": " << syrk_launches_
        << ", \"kernel.k_syrk_fx.algorithmic_bytes\": " << (fx_bytes + acc_bytes)
        << ", \"kernel.k_syrk_fx.limb_macs\": "
-       << (double)Ptot_ * N_ * (N_ + 1) / 2 * FX * FX * (Syrk::SYRK_TOOM5K ? 27.0 / 64 : Syrk::SYRK_TOOM4K ? 21.0 / 64 : Syrk::SYRK_TOOM4 ? 7.0 / 16 : Syrk::SYRK_TWO_LEVEL ? 9.0 / 16 : 0.75) // executed: 21 (FX/8)^2, 7 or 9 (FX/4)^2, or 3 (FX/2)^2 per product
+       << (double)Ptot_ * N_ * (N_ + 1) / 2 * FX * FX * (Syrk::SYRK_TOOM5K ? 81.0 / 256 : Syrk::SYRK_TOOM4K ? 21.0 / 64 : Syrk::SYRK_TOOM4 ? 7.0 / 16 : Syrk::SYRK_TWO_LEVEL ? 9.0 / 16 : 0.75) // executed: 81 (27 x 3 one-limb), 21 (FX/8)^2, 7 or 9 (FX/4)^2, or 3 (FX/2)^2 per product
        << ", \"kernel.k_syrk_fx.karatsuba_levels\": " << (Syrk::SYRK_TOOM4 ? 0 : Syrk::SYRK_TWO_LEVEL ? 2 : 1) << ", \"kernel.k_syrk_fx.toom4\": " << (Syrk::SYRK_TOOM4 ? 1 : 0) << ", \"kernel.k_syrk_fx.toom4k\": " << (Syrk::SYRK_TOOM4K ? 1 : 0) << ", \"kernel.k_syrk_fx.toom5k_lazy_carries\": " << (Syrk::SYRK_TOOM5K ? 1 : 0)
        << ", \"host_syncs\": " << host_syncs_ << ", \"launches\": " << launches_
        << ", \"iterations\": " << iteration_ << ", \"comm.world\": " << world_ << ", \"comm.ranks\": " << (comm_ ? comm_->ranks() : (world_ == 1 ? 1 : 0))

@@ -122,8 +122,8 @@ public:
   static constexpr int ACCW = 2 * FX + 2;
   static constexpr bool SYRK_TOOM4 = fx_toom4<FX>();         // seven (FX/4)^2 products per row pair (k_syrk_fx2<.., true> + k_syrk4_finish)
   static constexpr bool SYRK_TOOM4K = fx_toom4k<FX>();       // ... and one Karatsuba level below them: 21 (FX/8)^2 products (k_syrk_fx3)
-  static constexpr bool SYRK_TOOM5K = fx_toom5k<FX>();       // Toom-5 x Karatsuba on 28-bit limbs, lazy carries: 27 products of 2 x 2 limbs (k_syrk_fx3 in lazy mode + k_syrk5_finish)
-  static constexpr int SYRK_NPROD = fx_nprod<FX>();          // products per row pair of k_syrk_fx3
+  static constexpr bool SYRK_TOOM5K = fx_toom5k<FX>();       // Toom-5 x two Karatsuba levels on 28-bit limbs, lazy carries: 27 products of three one-limb sub-sweeps (k_syrk5_k2 + k_syrk5_finish)
+  static constexpr int SYRK_NPROD = fx_nprod<FX>();          // products per row pair of k_syrk_fx3 / k_syrk5_k2
   static constexpr int SYRK_EDGE = syrk_tile_edge<FX>();     // output tile of the syrk kernel in use
   static constexpr unsigned SYRK_SPLIT_ROWS = SYRK_TOOM4K ? 2560u : 0u; // rows per row split of k_syrk_fx3 at most (syrk_row_splits)
   static constexpr bool SYRK_TWO_LEVEL = fx_two_level<FX>() || SYRK_TOOM4; // piece-major image: nine (two Karatsuba levels) or seven pieces
@@ -137,6 +137,8 @@ public:
 #endif
   static constexpr int SYRK_RB = SYRK_TWO_LEVEL ? SDPB_SYRK2_RBG : (FX <= 24 ? 16 : 8);
   static constexpr size_t TILE_WORDS = (size_t)SYRK_PART_PLANES * SYRK_EDGE * SYRK_EDGE; // partial planes of one tile in one row split
+  static constexpr int SYRK5_ROWS = SDPB_SYRK5_ROWS; // rows per pass of k_syrk5_k2 (a divisor of SYRK_RB, which pads the image and aligns the splits)
+  static_assert(!SYRK_TOOM5K || SYRK_RB % SYRK5_ROWS == 0, "a split begins and the image ends at whole passes of k_syrk5_k2");
 
   explicit FxSyrk(int num_cus) : num_cus_(num_cus), rec_(&own_) {}
   // a workspace for another operand under the budgets of the solver's stage, reporting its calls to it
@@ -181,7 +183,7 @@ public:
   static size_t image_stride(size_t rows, size_t cols) { return std::max<size_t>(1, fx_image_stride<FX>(rows, cols, SYRK_RB)); }
   static size_t image_words_for(size_t rows, size_t cols) { return image_stride(rows, cols) * fx_planes<FX>() + 4; }
   static unsigned colsum_slices(size_t rows) { return (unsigned)std::min<size_t>(128, std::max<size_t>(1, cdiv(rows, 64))); }
-  // k_syrk_fx3: the 21 products of a (tile, row split) in one workgroup (1), one Toom-4 group each (7), or one product each (21)
+  // k_syrk_fx3 / k_syrk5_k2: the 21 (27) products of a (tile, row split) in one workgroup (1), one Toom group each (7, 9), or one product each
   static int syrk_group_split()
   {
     if(!SYRK_TOOM4K)
@@ -197,7 +199,8 @@ public:
   // that fit `budget_words`, and no split without rows
   int syrk_splits_for(int tiles, unsigned nrows, size_t budget_words) const
   {
-    const int slots = num_cus_ * syrk_waves_per_simd<FX>();
+    // workgroups the chip holds at once: of four wavefronts, or the one-wave workgroups of k_syrk5_k2
+    const int slots = num_cus_ * (SYRK_TOOM5K ? syrk5_wg_per_cu(SYRK5_ROWS) : syrk_waves_per_simd<FX>());
     int nsplit = syrk_row_splits(tiles * syrk_group_split(), nrows, slots, SYRK_RB, SYRK_SPLIT_ROWS);
     const size_t per_split = TILE_WORDS * tiles;
     if(budget_words && (size_t)nsplit * per_split > budget_words)
@@ -434,7 +437,10 @@ private:
         const dim3 grid(8 * cdiv((size_t)nt * nsplit, 8)), finish_grid(cdiv(total, WG));
         if constexpr(SYRK_TOOM4)
           {
-            if constexpr(SYRK_TOOM4K)
+            if constexpr(SYRK_TOOM5K)
+              launch(k_syrk5_k2<FX, SYRK5_ROWS>, dim3(8 * cdiv((size_t)nt * nsplit * gsplit, 8)), dim3(SYRK5_WG), stream, fx, win.stride, nrows, N, out,
+                     os, tl, nt, nsplit, rps, gsplit);
+            else if constexpr(SYRK_TOOM4K)
               launch(k_syrk_fx3<FX, SYRK_RB>, dim3(8 * cdiv((size_t)nt * nsplit * gsplit, 8)), dim3(WG), stream, fx, win.stride, nrows, N, out, os, tl,
                      nt, nsplit, rps, gsplit);
             else

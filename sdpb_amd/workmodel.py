@@ -70,18 +70,19 @@ def limbs_for(precision: int) -> int:
 
 
 def _fx(nl: int):
-    """(FX, image pieces in words per element, tile edge, planes one row split writes, staged rows, waves per SIMD)"""
+    """(FX, image pieces in words per element, tile edge, planes one row split writes, staged rows, resident workgroups per CU)"""
     fx = nl - 2
     if fx >= 14 and fx % 4:
         fx += 4 - fx % 4
     toom4 = fx >= 16 and fx % 4 == 0
     toom4k = fx in (16, 24, 32)
-    toom5k = fx == 16          # kernels.hpp: fx_toom5k (Toom-5 x Karatsuba on 28-bit limbs: 27 pieces of two words, 27 x 5 limbs per split)
+    toom5k = fx == 16          # kernels.hpp: fx_toom5k (Toom-5 x two Karatsuba levels on 28-bit limbs: 27 pieces of three words x0, x1, x0 + x1; 27 x 5 limbs per split)
     two = fx % 4 == 0
-    words = 54 if toom5k else 21 * (fx // 8) if toom4k else 7 * (fx // 4) if toom4 else 9 * (fx // 4) if two else 3 * (fx // 2)
+    words = 81 if toom5k else 21 * (fx // 8) if toom4k else 7 * (fx // 4) if toom4 else 9 * (fx // 4) if two else 3 * (fx // 2)
     planes = 135 if toom5k else 21 * (2 * (fx // 8) + 1) if toom4k else 7 * (2 * (fx // 4) + 1) if toom4 else 2 * fx + 2
     rb = (16 if fx >= 32 else 32) if two else (16 if fx <= 24 else 8)
-    waves = 3 if toom4k else (3 if fx <= 16 else 2)
+    # workgroups a CU holds: four-wave workgroups by registers; the one-wave workgroups of k_syrk5_k2 by LDS (kernels.hpp: syrk5_wg_per_cu, 16 rows per pass)
+    waves = 16 if toom5k else 3 if toom4k else (3 if fx <= 16 else 2)
     return fx, words, 32 if toom4k else 16, planes, rb, waves, toom4, toom4k
 
 
@@ -179,7 +180,7 @@ def planned_footprint(dims, num_points, N, precision, owners=None, rank=0, world
     ntile = tiles * (tiles + 1) // 2
 
     def planes_unbounded(r):
-        ns = syrk_row_splits(ntile * (21 if toom4k else 1), r, num_cus * waves, rb, 2560 if toom4k else 0) if r else 1
+        ns = syrk_row_splits(ntile * ((27 if fx == 16 else 21) if toom4k else 1), r, num_cus * waves, rb, 2560 if toom4k else 0) if r else 1
         return ns * planes * ntile * edge * edge * 4 if (ns > 1 or toom4) else 0
     unbounded = planes_unbounded(chunk_rows)
     budget = max(window - min(image, window // 2), 4)
